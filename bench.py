@@ -11,8 +11,8 @@ Workloads:
      privacy id (rank r holds the privacy ids = r mod N).
   c2 (BASELINE configs[1]): 1e8 rows per GPU, 1e6 privacy ids, 1e5 uniform
      partitions, values N(5, 3) clipped to [0, 10], L0 = 8, Linf = 2.  Weak
-     scaling.  At N = 1 with the default workload it also runs as the
-     `secondary` object of the JSON line.
+     scaling.  At N = 1 with the default workload and --full it also runs as
+     the `secondary` object of the JSON line.
   c4 (BASELINE configs[3]): VARIANCE + PRIVACY_ID_COUNT,
      Gaussian noise, private partition selection, 1e7 uniform partitions,
      values U(0, 10), L0 = 4, Linf = 2; 1.25e8 rows and 1.25e7 privacy ids
@@ -34,9 +34,21 @@ the kept-partition count on the host.  Inputs are resident in HBM before
 timing starts.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5]
+                       [--dump-outputs DIR] [--full]
   With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts
   `python -m torch.distributed.run --nproc-per-node N` on itself as a child
   process (before touching the GPU) and exits with its status.
+
+A plain run does what the headline figure needs and no more: it generates the
+inputs, warms up, times the K steps, writes the outputs of the last timed step
+(--dump-outputs) and prints the JSON line: value (rows/s), ms_per_step and the
+whole-step share of the HBM peak (path_roofline).  --full adds every other
+measurement and check, each in passes of its own after the timed steps: the
+key-error check of the data, per-kernel times (the library's profiler) with
+their algorithmic and PMC bytes, the work statistics and the plan, steps timed
+one by one, the public-API timing, the privacy-id sharding check at N > 1, the
+C2 secondary run and the CPU baselines (--no-api, --no-secondary and
+--no-cpu-baseline leave single ones out of a --full run).
 """
 import argparse
 import json
@@ -134,7 +146,7 @@ MIN_VALUE, MAX_VALUE = 0.0, 10.0
 EPS, DELTA = 1.0, 1e-6
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--privacy-ids", type=int, default=0,
@@ -175,7 +187,14 @@ def parse():
                          "reduce-scatter, as every rank of the N-GPU run does (VERDICT r04 #4)")
     ap.add_argument("--no-api", dest="api", action="store_false",
                     help="skip the public-API timing (DPEngine.aggregate on ColumnarBackend)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (per-kernel "
+                         "times and bytes, work statistics, steps timed one by one, the public-API timing, "
+                         "the sharding check at N > 1, the C2 secondary run, the CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of the rows when they exceed DUMP_BUDGET_BYTES in all)")
+    return ap.parse_args(argv)
 
 
 def maybe_spawn(args):
@@ -192,6 +211,60 @@ def maybe_spawn(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.exit(subprocess.call(cmd, env=env))
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files of one rank together stay below this
+DUMP_SAMPLE_SEED = 20261019
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: writes each array of `arrays` (name -> NumPy array or
+    torch tensor, rows along the first axis) as out_dir/<name>.npy
+    (<name>.rank<r>.npy at N > 1), float32 kept and everything else as
+    float64.  When the arrays exceed DUMP_BUDGET_BYTES in all, every array
+    keeps the same share of its rows: a sorted sample drawn from
+    DUMP_SAMPLE_SEED and the row count alone, so arrays of equal length keep
+    the same rows and two runs keep the same rows.  Returns the names written."""
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        host[name] = np.atleast_1d(a if a.dtype == np.float32 else a.astype(np.float64))
+    total = sum(a.nbytes for a in host.values())
+    share = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {}
+    for name, a in host.items():
+        n = a.shape[0]
+        if share < 1.0 and n > 1:
+            if n not in rows:
+                rng = np.random.default_rng([DUMP_SAMPLE_SEED, n])
+                rows[n] = np.sort(rng.choice(n, size=max(1, int(n * share)), replace=False))
+            a = a[rows[n]]
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if world > 1 else "") + ".npy"),
+                np.ascontiguousarray(a))
+    return sorted(host)
+
+
+def max_over_ranks(elapsed, world, device):
+    """The slowest rank's time of the timed region (the value itself at N = 1)."""
+    if world == 1:
+        return elapsed
+    import torch
+    import torch.distributed as dist
+    t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return float(t.item())
+
+
+def path_roofline_of(path_bytes, ms_per_step, traffic=None):
+    """The headline fraction: the step's compulsory bytes over its whole time."""
+    path_gbs = path_bytes / (ms_per_step * 1e-3) / 1e9
+    return {"achieved": path_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": path_gbs / HBM_PEAK_GBS,
+            "bytes_per_step": path_bytes, "traffic_per_step": sum(traffic.values()) if traffic else None}
 
 
 def build_plan(l0, linf):
@@ -424,7 +497,7 @@ def run_api_workload(args, workload, world, rank, device):
     # the default privacy_id_sharding="verify" on the dataset-wide ids, once,
     # before timing (the steps below pass "trusted": the check does not
     # change between steps)
-    verify_ms = verify_sharding(pid, world, rank, U)
+    verify_ms = verify_sharding(pid, world, rank, U) if args.full else None
     table = pdp.ColumnTable({"pid": pid, "pk": pk, "v": value}, n_privacy_ids=U, n_partitions=P)
     strategy = {"truncated_geometric": pdp.PartitionSelectionStrategy.TRUNCATED_GEOMETRIC,
                 "gaussian": pdp.PartitionSelectionStrategy.GAUSSIAN_THRESHOLDING,
@@ -449,7 +522,7 @@ def run_api_workload(args, workload, world, rank, device):
 
     counter = [0]
 
-    def step():
+    def step(keep=False):
         # seeded per step (bench.py --seed): the line is reproducible
         counter[0] += 1
         acc = pdp.NaiveBudgetAccountant(total_epsilon=EPS, total_delta=DELTA)
@@ -457,7 +530,8 @@ def run_api_workload(args, workload, world, rank, device):
                                      seed=args.seed + counter[0])
         sink = pdp.DPEngine(acc, backend).aggregate(table, params, ext)
         acc.compute_budgets()
-        return len(sink.collect()), backend
+        res = sink.collect()
+        return len(res), backend, (res if keep else None)  # keep: the result itself, for --dump-outputs
 
     for _ in range(max(1, args.warmup)):
         step()
@@ -467,21 +541,43 @@ def run_api_workload(args, workload, world, rank, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     kept = 0
-    for _ in range(args.steps):
-        kept, backend = step()
+    for i in range(args.steps):
+        kept, backend, res = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(res.columns, partition_keys=res.partition_keys), rank, world)
+    del res
+    strat = args.strategy.replace("_", " ") + ("" if args.strategy == "truncated_geometric" else " thresholding")
+    desc = (f"C4: DPEngine.aggregate VARIANCE+PRIVACY_ID_COUNT, Gaussian, private partitions ({strat}), "
+            f"L0=4, Linf=2, uniform keys" if workload == "c4" else
+            f"C5: DPEngine.aggregate COUNT+SUM+MEAN, Laplace, private partitions ({strat}), L0=4, Linf=2, rows per "
+            "privacy id Pareto(1.5) capped at 1e6, Zipf(1.1) partition keys, lognormal values in [0, 20]")
+    config = {"workload": f"{desc}, {n:.3g} rows and {U:.3g} privacy ids per GPU, {P:.3g} partitions",
+              "rows_per_gpu": n, "privacy_ids_per_gpu": U, "partitions": P,
+              "parallelism": f"rows sharded by privacy_id over {world} GPU(s)",
+              "timed": "public API per step: DPEngine.aggregate + compute_budgets() + collect()"}
+    # compulsory bytes (SURVEY §8(d)): the three input columns once, and per
+    # kept partition its key, accumulators and output metrics
+    k_out = 2 if workload == "c4" else 3
+    if not args.full:
+        # the accumulator fields of X.new_accumulators for the spec the API built
+        flags = backend.last_bounding.flags
+        n_fields = sum(bool(flags & f) for f in (N.ACC_SUM | N.SUM_PER_PARTITION, N.ACC_NSUM, N.ACC_NSUM2))
+        elapsed = max_over_ranks(elapsed, world, device)
+        ms_per_step = elapsed / args.steps * 1e3
+        path_bytes = 24.0 * n + kept * (8 + 8 * (2 + n_fields) + 8 * k_out)
+        return {"value": n * world * args.steps / elapsed, "ms_per_step": ms_per_step, "config": config,
+                "roofline": None, "path_roofline": path_roofline_of(path_bytes, ms_per_step), "kernels": None,
+                "bound_plan": None, "seed": args.seed, "partitions_kept": kept}
     N.profiler_enable(True)
     for _ in range(args.steps):
         step()
     kernels = N.profiler_report()
     N.profiler_enable(False)
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+    elapsed = max_over_ranks(elapsed, world, device)
     info = backend.last_plan_info
     # kept pairs / rows and the plan's stats for the byte accounting: one more
     # bounding pass with the spec the API built (untimed)
@@ -511,30 +607,16 @@ def run_api_workload(args, workload, world, rank, device):
             traffic.pop(k, None)  # out of traffic_per_step too
         table[k] = e
     dom = max(kernel_ms, key=lambda k: kernel_ms[k] * launches[k])
-    # compulsory bytes (SURVEY §8(d)): the three input columns once, and per
-    # kept partition its key, accumulators and output metrics
-    k_out = 2 if workload == "c4" else 3
     path_bytes = 24.0 * n + kept * (8 + 8 * (2 + n_fields) + 8 * k_out)
-    path_gbs = path_bytes / (ms_per_step * 1e-3) / 1e9
-    strat = args.strategy.replace("_", " ") + ("" if args.strategy == "truncated_geometric" else " thresholding")
-    desc = (f"C4: DPEngine.aggregate VARIANCE+PRIVACY_ID_COUNT, Gaussian, private partitions ({strat}), "
-            f"L0=4, Linf=2, uniform keys" if workload == "c4" else
-            f"C5: DPEngine.aggregate COUNT+SUM+MEAN, Laplace, private partitions ({strat}), L0=4, Linf=2, rows per "
-            "privacy id Pareto(1.5) capped at 1e6, Zipf(1.1) partition keys, lognormal values in [0, 20]")
     return {
         "value": n * world * args.steps / elapsed,
         "ms_per_step": ms_per_step,
-        "config": {"workload": f"{desc}, {n:.3g} rows and {U:.3g} privacy ids per GPU, {P:.3g} partitions",
-                   "rows_per_gpu": n, "privacy_ids_per_gpu": U, "partitions": P,
-                   "parallelism": f"rows sharded by privacy_id over {world} GPU(s)",
-                   "timed": "public API per step: DPEngine.aggregate + compute_budgets() + collect()"},
+        "config": config,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": table[dom].get("achieved_gbs"),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": table[dom].get("frac"),
                      "traffic": traffic.get(dom), "traffic_source": traffic_src, "traffic_refused": traffic_refused,
                      "bytes_per_launch": alg.get(dom), "avg_ms": kernel_ms[dom]},
-        "path_roofline": {"achieved": path_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": path_gbs / HBM_PEAK_GBS, "bytes_per_step": path_bytes,
-                          "traffic_per_step": sum(traffic.values()) if traffic else None},
+        "path_roofline": path_roofline_of(path_bytes, ms_per_step, traffic),
         "kernels": table, "kept_pairs": kept_pairs, "kept_rows": kept_rows,
         "bound_plan": None if info is None else {
             "algorithm": info.algorithm, "bucket_bits": info.bucket_bits, "n_buckets": info.n_buckets,
@@ -572,8 +654,9 @@ def run_hist_workload(args, world, rank, device):
     val = (torch.randn(n, generator=g, device=device, dtype=torch.float64) * 3.0 + 5.0).clamp_(MIN_VALUE, MAX_VALUE)
     ws = X.BoundWorkspace()
 
-    def step():
-        X.dataset_histograms(pid, pk, val, n_privacy_ids=U, n_partitions=P, workspace=ws)
+    def step(keep=False):
+        out = X.dataset_histograms(pid, pk, val, n_privacy_ids=U, n_partitions=P, workspace=ws)
+        return out if keep else None  # keep: the bin arrays, for --dump-outputs
 
     for _ in range(max(1, args.warmup)):
         step()
@@ -582,21 +665,32 @@ def run_hist_workload(args, world, rank, device):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        bins = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v for k, v in bins.items() if k != "workspace"}, rank, world)
+    del bins
+    elapsed = max_over_ranks(elapsed, world, device)
+    config = {"workload": f"dataset histograms (compute_dataset_histograms, all seven) over {n:.3g} rows "
+                          f"per GPU, {U:.3g} privacy ids, {P:.3g} partitions, fp64 values",
+              "rows_per_gpu": n, "privacy_ids": U, "partitions": P,
+              "parallelism": f"rows sharded by privacy_id over {world} GPU(s)"}
+    if not args.full:
+        ms_per_step = elapsed / args.steps * 1e3
+        path = path_roofline_of(24.0 * n, ms_per_step)
+        del path["traffic_per_step"]
+        return {"value": n * world * args.steps / elapsed, "ms_per_step": ms_per_step, "config": config,
+                "roofline": None, "path_roofline": path, "kernels": None, "bound_plan": None,
+                "partitions_kept": None, "api": None}
     N.profiler_enable(True)
     for _ in range(args.steps):
         step()
     kernels = N.profiler_report()
     N.profiler_enable(False)
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
     pairs = int(torch.unique(pid * P + pk).numel())  # distinct (privacy id, partition) pairs, untimed
     del pid, pk, val, ws
     kernel_ms = {k: v[0] / v[1] for k, v in kernels.items()}
@@ -628,10 +722,7 @@ def run_hist_workload(args, world, rank, device):
     return {
         "value": n * world * args.steps / elapsed,
         "ms_per_step": ms_per_step,
-        "config": {"workload": f"dataset histograms (compute_dataset_histograms, all seven) over {n:.3g} rows "
-                               f"per GPU, {U:.3g} privacy ids, {P:.3g} partitions, fp64 values",
-                   "rows_per_gpu": n, "privacy_ids": U, "partitions": P,
-                   "parallelism": f"rows sharded by privacy_id over {world} GPU(s)"},
+        "config": config,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": table[dom].get("achieved_gbs"),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": table[dom].get("frac"),
                      "traffic": traffic.get(dom), "traffic_source": traffic_src, "traffic_refused": traffic_refused,
@@ -770,7 +861,7 @@ def run_workload(args, workload, world, rank, device, pmc_file):
     # rank r holds the dataset-wide ids owned_identities(U, world, r): checked
     # once with the library's default verify (it raises on an id held by two
     # ranks); the kernels take the local codes
-    verify_ms = verify_sharding(pid, world, rank, U)
+    verify_ms = verify_sharding(pid, world, rank, U) if args.full else None
 
     P_pad, _ = parallel.partition_slices(P, world)
     ws = X.BoundWorkspace()
@@ -778,8 +869,9 @@ def run_workload(args, workload, world, rank, device, pmc_file):
     plan = X.bound_plan(n, U, P_pad, bounding, **tune)
     acc = X.new_accumulators(P_pad, bounding, device)
     seed_base = args.seed
+    kept_out = {}  # --dump-outputs: the last timed step's outputs
 
-    def step(i):
+    def step(i, keep=False):
         X.zero_accumulators(acc)  # one fill: the fields share a block
         X.bound_and_reduce(pid, pk, value, n_privacy_ids=U, n_partitions=P_pad, bounding=bounding,
                            seed=seed_base + i, row_offset=rank * n, acc=acc, workspace=ws,
@@ -789,10 +881,12 @@ def run_workload(args, workload, world, rank, device, pmc_file):
         mine, first = parallel.exchange_accumulators(acc, int_bound=n * world)
         if share > 1:  # one rank's share: its slice of the partitions (rank 0's)
             mine = {k: (None if t is None else t[:P_pad // share]) for k, t in mine.items()}
-        _, _, n_kept = X.select_and_noise(mine, selection=selection, ops=ops, n_cols=3,
-                                          seed_select=seed_base ^ (i * 7919 + 1),
-                                          seed_noise=seed_base ^ (i * 104729 + 2),
-                                          partition_offset=first, sync_count=False)
+        index, out, n_kept = X.select_and_noise(mine, selection=selection, ops=ops, n_cols=3,
+                                                seed_select=seed_base ^ (i * 7919 + 1),
+                                                seed_noise=seed_base ^ (i * 104729 + 2),
+                                                partition_offset=first, sync_count=False)
+        if keep:  # --dump-outputs: what the step's caller receives, and the accumulators behind it
+            kept_out.update(mine, partition_index=index, metrics=out)
         return n_kept  # a device count: no host round trip inside a step
 
     for i in range(args.warmup):
@@ -804,12 +898,43 @@ def run_workload(args, workload, world, rank, device, pmc_file):
     t0 = time.perf_counter()
     kept = 0
     for i in range(args.steps):
-        kept = step(args.warmup + i)
+        kept = step(args.warmup + i, keep=bool(args.dump_outputs) and i == args.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kept = int(kept)
+    if args.dump_outputs:
+        # the kept partitions' indices and their noisy metric columns (one row
+        # per kept partition), and the accumulators the step selected from
+        # (they are the step's own until the next step zeroes them)
+        index, out = kept_out.pop("partition_index"), kept_out.pop("metrics")
+        dump_outputs(args.dump_outputs, dict({"acc_" + k: t for k, t in kept_out.items()},
+                                             partition_index=index[:kept], metrics=out[:, :kept].T),
+                     rank, world)
+        del index, out
+        kept_out.clear()
+    w = C3 if workload == "c3" else C2
+    config = {
+        "workload": (f"{workload.upper()}: DPEngine.aggregate COUNT+SUM+MEAN, Laplace, private partitions "
+                     f"(truncated geometric), L0={w['l0']}, Linf={w['linf']}, "
+                     + (f"{n * world:.3g} rows in total, Zipf({C3['zipf']}) partition keys"
+                        if workload == "c3" else f"{n:.3g} rows per GPU, uniform keys")
+                     + (f", {args.small_ids:g} of the privacy ids with 1-3 rows"
+                        if workload == "c3" and args.small_ids else "")),
+        "rows_per_gpu": n, "privacy_ids_per_gpu": U, "partitions": P,
+        "parallelism": (f"rows sharded by privacy_id over {world} GPU(s)" if share == 1 else
+                        f"ONE RANK'S SHARE of a {share}-GPU run on one GPU: rows and privacy ids / {share}, "
+                        f"selection + noise over P / {share} partitions, the reduce-scatter not included"),
+    }
+    path_bytes = 24.0 * n + kept * (8 + 8 * 3 + 8 * 3)  # SURVEY §8(d) compulsory bytes
+    if not args.full:
+        elapsed = max_over_ranks(elapsed, world, device)
+        ms_per_step = elapsed / args.steps * 1e3
+        del pid, pk, value, acc, ws
+        return {"value": n * world * args.steps / elapsed, "ms_per_step": ms_per_step, "workload_name": workload,
+                "config": config, "roofline": None, "path_roofline": path_roofline_of(path_bytes, ms_per_step),
+                "kernels": None, "bound_plan": None, "seed": args.seed, "partitions_kept": kept, "api": None}
     # key-error check of the data once (outside the timed region)
     X.bound_and_reduce(pid, pk, value, n_privacy_ids=U, n_partitions=P_pad, bounding=bounding, seed=1,
                        row_offset=rank * n, acc=acc, workspace=ws, check_keys=True, **tune)
@@ -840,10 +965,7 @@ def run_workload(args, workload, world, rank, device, pmc_file):
     if feedback and feedback["unsieved"] and not args.sieve:
         plan = X.bound_plan(n, U, P_pad, bounding, **dict(tune, sieve=-1))
     api = api_timing(args, workload, pid, pk, value, U, P, ws) if (world == 1 and args.api) else None
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+    elapsed = max_over_ranks(elapsed, world, device)
     del pid, pk, value, acc, ws
 
     kernel_ms = {k: v[0] / v[1] for k, v in kernels.items()}  # average ms per launch
@@ -865,36 +987,19 @@ def run_workload(args, workload, world, rank, device, pmc_file):
             traffic.pop(k, None)  # out of traffic_per_step too
         table[k] = e
     dom = max(kernel_ms, key=lambda k: kernel_ms[k] * launches[k])
-    path_bytes = 24.0 * n + kept * (8 + 8 * 3 + 8 * 3)  # SURVEY §8(d) compulsory bytes
-    path_gbs = path_bytes / (ms_per_step * 1e-3) / 1e9
-    w = C3 if workload == "c3" else C2
     return {
         "value": total_rows / elapsed,
         "ms_per_step": ms_per_step,
         "workload_name": workload,
-        "config": {
-            "workload": (f"{workload.upper()}: DPEngine.aggregate COUNT+SUM+MEAN, Laplace, private partitions "
-                         f"(truncated geometric), L0={w['l0']}, Linf={w['linf']}, "
-                         + (f"{n * world:.3g} rows in total, Zipf({C3['zipf']}) partition keys"
-                            if workload == "c3" else f"{n:.3g} rows per GPU, uniform keys")
-                         + (f", {args.small_ids:g} of the privacy ids with 1-3 rows"
-                            if workload == "c3" and args.small_ids else "")),
-            "rows_per_gpu": n, "privacy_ids_per_gpu": U, "partitions": P,
-            "parallelism": (f"rows sharded by privacy_id over {world} GPU(s)" if share == 1 else
-                            f"ONE RANK'S SHARE of a {share}-GPU run on one GPU: rows and privacy ids / {share}, "
-                            f"selection + noise over P / {share} partitions, the reduce-scatter not included"),
-        },
+        "config": config,
         "roofline": {  # dominant kernel, its OWN algorithmic bytes
             "bound": "hbm", "kernel": dom,
             "achieved": table[dom].get("achieved_gbs"), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": table[dom].get("frac"), "traffic": traffic.get(dom), "traffic_source": traffic_src,
             "traffic_refused": traffic_refused, "bytes_per_launch": alg.get(dom), "avg_ms": kernel_ms[dom],
         },
-        "path_roofline": {  # the headline fraction: 24 B/row compulsory over the whole step
-            "achieved": path_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": path_gbs / HBM_PEAK_GBS,
-            "bytes_per_step": path_bytes,
-            "traffic_per_step": sum(traffic.values()) if traffic else None,
-        },
+        # the headline fraction: 24 B/row compulsory over the whole step
+        "path_roofline": path_roofline_of(path_bytes, ms_per_step, traffic),
         "kernels": table,
         "bound_plan": {"algorithm": plan.algorithm, "bucket_bits": plan.bucket_bits,
                        "n_buckets": plan.n_buckets, "lds_bytes": plan.lds_bytes,
@@ -913,8 +1018,8 @@ def run_workload(args, workload, world, rank, device, pmc_file):
     }
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     maybe_spawn(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -964,6 +1069,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": r["ms_per_step"],
         "higher_is_better": True,
         "scaling": "strong" if args.workload == "c3" else "weak",
@@ -992,13 +1098,16 @@ def main():
         "cpu_baseline_strong": None,
         "cpu_baseline_c1": None,
     }
-    if world == 1 and args.workload == "c3" and not args.no_secondary and not args.rows and not args.share_of:
+    if (args.full and world == 1 and args.workload == "c3" and not args.no_secondary and not args.rows
+            and not args.share_of):
         torch.cuda.empty_cache()
-        s = run_workload(args, "c2", 1, 0, device, PMC_SUMMARY["c2"])
+        # (--dump-outputs holds the headline workload's outputs only)
+        s = run_workload(argparse.Namespace(**dict(vars(args), dump_outputs=None)), "c2", 1, 0, device,
+                         PMC_SUMMARY["c2"])
         result["secondary"] = {k: s[k] for k in ("value", "ms_per_step", "config", "roofline",
                                                  "path_roofline", "kernels", "bound_plan", "api")}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("c3", "c2", "hist"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("c3", "c2", "hist"):
         # after the GPU measurements, in a child process (no GPU state there):
         # its ~30 s of host work can neither precede nor overlap the timed steps
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--workload",

@@ -48,6 +48,51 @@ def test_pmc_join_checks_the_source_tree(tmp_path):
     assert bench.load_pmc(str(f), "c3", 1000, 2) == ({}, None, None)  # N > 1: never joined
 
 
+def test_plain_run_is_the_default():
+    """--full and --dump-outputs are off unless asked for."""
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 2)
+    args = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert args.full and args.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    keys = np.arange(10, dtype=np.int64) * 3
+    names = bench.dump_outputs(str(tmp_path), {"keys": keys, "f32": np.ones((10, 2), np.float32),
+                                               "scalar": np.int64(5), "absent": None})
+    assert names == ["f32", "keys", "scalar"]
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["f32.npy", "keys.npy", "scalar.npy"]
+    got = np.load(tmp_path / "keys.npy")
+    assert got.dtype == np.float64 and (got == keys).all()
+    assert np.load(tmp_path / "f32.npy").dtype == np.float32
+    assert np.load(tmp_path / "scalar.npy").tolist() == [5.0]
+
+
+def test_dump_outputs_samples_the_same_rows_within_the_budget(tmp_path, monkeypatch):
+    """Past the byte budget every array keeps the same seeded share of its
+    rows: arrays of one length keep the same rows, and so do two runs."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    n = 1000
+    arrays = {"keys": np.arange(n), "cols": np.arange(n)[:, None] * np.ones((1, 3)), "other": np.arange(77.0)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, rank=1, world=2)
+    a = {k: np.load(tmp_path / "a" / f"{k}.rank1.npy") for k in arrays}
+    b = {k: np.load(tmp_path / "b" / f"{k}.rank1.npy") for k in arrays}
+    assert sum(v.nbytes for v in a.values()) <= 4000
+    assert 0 < len(a["keys"]) < n and len(a["keys"]) == len(a["cols"]) and 0 < len(a["other"]) < 77
+    assert (np.diff(a["keys"]) > 0).all()
+    assert (a["cols"] == a["keys"][:, None]).all()  # the same rows of both
+    assert all((a[k] == b[k]).all() for k in arrays)
+
+
 def test_pmc_kernel_names_match_the_library_profiler():
     """rocprofv3 names the template instances; the PMC summary must file them
     under the library profiler's names, or bench.py joins no bytes for them."""

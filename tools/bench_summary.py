@@ -5,6 +5,10 @@ import sys
 
 
 def show(tag, r):
+    if not r.get("roofline"):  # a plain run: the per-kernel figures come with bench.py --full
+        print(f"{tag}: {r['ms_per_step']:.3f} ms/step  {r['value']:.4g} rows/s  path frac "
+              f"{r['path_roofline']['frac']:.3f}")
+        return
     print(f"{tag}: {r['ms_per_step']:.3f} ms/step  {r['value']:.4g} rows/s  path frac "
           f"{r['path_roofline']['frac']:.3f}  dominant {r['roofline']['kernel']} frac "
           f"{(r['roofline']['frac'] or 0):.3f}  plan {r.get('bound_plan')}")

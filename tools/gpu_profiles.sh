@@ -19,11 +19,11 @@ for W in ${WORKLOADS:-c3 c2 c4 c5 hist}; do
     hist) N=100000000; ARGS="--workload hist" ;;
   esac
   mkdir -p $OUT/$W
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/$W/stats -o run --output-format csv -- python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline $ARGS > $OUT/$W/stats.log 2>&1 || { tail -20 $OUT/$W/stats.log; echo "ROCPROF $W FAILED"; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/$W/stats -o run --output-format csv -- python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $ARGS > $OUT/$W/stats.log 2>&1 || { tail -20 $OUT/$W/stats.log; echo "ROCPROF $W FAILED"; exit 1; }
   find $OUT/$W/stats -name "*kernel_stats.csv" -exec cp {} $OUT/${W}_kernel_stats.csv \;
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout -s KILL 300 rocprofv3 --pmc $C -d $OUT/$W/pmc/$C -o run --output-format csv -- python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline $ARGS > $OUT/$W/pmc_$C.log 2>&1 || { tail -20 $OUT/$W/pmc_$C.log; echo "PMC $W $C FAILED"; exit 1; }
+    timeout -s KILL 300 rocprofv3 --pmc $C -d $OUT/$W/pmc/$C -o run --output-format csv -- python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $ARGS > $OUT/$W/pmc_$C.log 2>&1 || { tail -20 $OUT/$W/pmc_$C.log; echo "PMC $W $C FAILED"; exit 1; }
   done
-  python3 tools/pmc_summary.py $OUT/$W/pmc $OUT/${W}_pmc.json "$W n=$N bench.py --steps 3 --warmup 1 $ARGS" $OUT/$W/pmc_FETCH_SIZE.log || exit 1
+  python3 tools/pmc_summary.py $OUT/$W/pmc $OUT/${W}_pmc.json "$W n=$N bench.py --full --steps 3 --warmup 1 $ARGS" $OUT/$W/pmc_FETCH_SIZE.log || exit 1
   echo "$W profiled"
 done

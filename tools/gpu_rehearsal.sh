@@ -8,8 +8,8 @@ T=${1:-rehearsal}
 OUT=gpurun_out/$T
 mkdir -p $OUT
 export PDP_BENCH_BACKEND=gloo
-timeout -k 10 400 python -u bench.py --workload c4 --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/c4.json 2> $OUT/c4.err || { echo "c4 failed"; tail -20 $OUT/c4.err; exit 1; }
-timeout -k 10 400 python -u bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-api > $OUT/c3.json 2> $OUT/c3.err || { echo "c3 failed"; tail -20 $OUT/c3.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --workload c4 --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/c4.json 2> $OUT/c4.err || { echo "c4 failed"; tail -20 $OUT/c4.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-api > $OUT/c3.json 2> $OUT/c3.err || { echo "c3 failed"; tail -20 $OUT/c3.err; exit 1; }
 python3 - $OUT <<'PY'
 import json, sys
 for w in ("c4", "c3"):

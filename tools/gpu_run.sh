@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU lease: [pytest selection] [smoke] [bench lines].  Results under gpurun_out/$TAG.
 #   TAG=r6a TESTS="tests/test_gpu_sieve.py tests/test_gpu_api.py" SMOKE=1 \
-#   BENCH="main|--steps 20 --warmup 5;share8|--share-of 8 --no-api --no-cpu-baseline" tools/gpu_run.sh
+#   BENCH="main|--full --steps 20 --warmup 5;share8|--share-of 8 --steps 20 --warmup 5" tools/gpu_run.sh
 # Every GPU step has its own time limit; the first failure ends the script.
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"

@@ -9,7 +9,7 @@ mkdir -p $OUT
 for pass in $(seq 1 ${ROUNDS:-2}); do
 for so in abv/*.so; do
   v=$(basename $so .so)
-  PIPELINEDP_AMD_LIB=$PWD/$so timeout -k 10 240 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline $BENCH_ARGS > $OUT/$v.$pass.log 2>&1 || { echo "variant $v failed"; tail -5 $OUT/$v.$pass.log; exit 1; }
+  PIPELINEDP_AMD_LIB=$PWD/$so timeout -k 10 240 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $BENCH_ARGS > $OUT/$v.$pass.log 2>&1 || { echo "variant $v failed"; tail -5 $OUT/$v.$pass.log; exit 1; }
   python3 - $OUT/$v.$pass.log $v.$pass <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")][-1]
