@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 14
+#define PDP_ABI_VERSION 15
 
 /* error codes */
 #define PDP_OK 0
@@ -312,6 +312,63 @@ int pdp_noise_metrics(const pdp_metric_op* ops, int32_t n_ops, const int64_t* in
                       const pdp_partition_accumulators* acc, int32_t sum_is_int,
                       const double* noised_count, double* out, int64_t out_stride,
                       uint64_t seed, void* stream);
+
+/* VECTOR_SUM (VectorSumCombiner, combiners.py:800-847): one double[vector_size]
+ * per row, summed per partition over the rows the bounder keeps (no per-row
+ * clipping); the partition's total is clipped and noised per coordinate by
+ * pdp_vector_sum_metrics.  vector_size in [1, PDP_MAX_VECTOR_SIZE]. */
+#define PDP_MAX_VECTOR_SIZE 4096
+
+/* NormKind (aggregate_params.py NormKind; dp_computations._clip_vector :197-209) */
+#define PDP_NORM_LINF 0 /* clip(v, -max_norm, max_norm) per coordinate */
+#define PDP_NORM_L1 1   /* v * min(1, max_norm / sum |v_j|) */
+#define PDP_NORM_L2 2   /* v * min(1, max_norm / sqrt(sum v_j^2)) */
+
+/* Philox stream slot of the vector-sum noise.  pdp_noise_metrics uses the slots
+ * (op << 4) | mechanism < 0x80 and pdp_add_noise 0x41444E00; this one ("VECS")
+ * collides with neither, so a vector sum noised with the seed of the scalar
+ * metrics still draws independent noise. */
+#define PDP_VECTOR_SUM_SLOT 0x56454353
+
+/* Bytes of device workspace for pdp_bound_contributions followed by
+ * pdp_reduce_vector_sum: the pair table's workspace (pdp_bound_workspace_bytes)
+ * plus the kept-row list (8 B per row), the per-partition counts and offsets
+ * and the partial sums of long partitions. */
+int pdp_vector_sum_workspace_bytes(const pdp_bound_config* cfg, int32_t vector_size, uint64_t* bytes);
+
+/* VectorSumCombiner.create_accumulator per kept pair, merged per partition
+ * (combiners.py:809-830): vector_acc[p][j] += the sum over the kept rows i of
+ * partition p of vectors[i][j].  vectors: row-major double[n_rows][vector_size];
+ * vector_acc: row-major double[n_partitions][vector_size], ADDED to.
+ * Must follow pdp_bound_contributions on the same workspace (of at least
+ * pdp_vector_sum_workspace_bytes) and stream, with the same key columns and
+ * pk_allowed, and a cfg that resolves to PDP_ALGO_PAIR_TABLE (any other plan:
+ * PDP_E_UNSUPPORTED); cfg->value_kind may be PDP_VALUE_NONE.  A row is kept
+ * iff the pair table kept it: keys in range and partition allowed, among its
+ * privacy id's max_contributions rows, its pair among the id's l0 pairs, and
+ * the row among its pair's linf rows (rows_are_units: every valid allowed
+ * row).  Out-of-range keys set bit 0 of the error word and are skipped.  The
+ * kept rows are counting-sorted by partition (no value traffic) and summed by
+ * waves whose lanes run across coordinates; a partition with many rows is
+ * split over waves and its partial sums are combined by a second kernel, so
+ * no floating-point atomic is used.  Sums may depend on the floating-point
+ * summation order (as with PDP_MERGE_RANGES), on nothing else. */
+int pdp_reduce_vector_sum(const pdp_bound_config* cfg, const int64_t* privacy_id, const int64_t* partition_key,
+                          const uint8_t* pk_allowed, const double* vectors, int32_t vector_size, void* workspace,
+                          uint64_t workspace_bytes, double* vector_acc, void* stream);
+
+/* VectorSumCombiner.compute_metrics (combiners.py:832-838 ->
+ * dp_computations.add_noise_vector :212-229) for the kept partitions: for each
+ * i < n_kept with p = index[i], vector_acc[p] is clipped by `norm_kind`
+ * (PDP_NORM_*; an all-zero vector has coefficient 1, never NaN) and
+ *   out[i * vector_size + j] = noise(clipped[j]),
+ * the secure mechanism `noise` (host pointer; granularity 0 = clip only) on
+ * the Philox streams (seed, (partition_offset + p) * vector_size + j,
+ * PDP_VECTOR_SUM_SLOT).  n_kept_dev as in pdp_noise_metrics. */
+int pdp_vector_sum_metrics(const double* vector_acc, int32_t vector_size, int32_t norm_kind, double max_norm,
+                           const pdp_noise_params* noise, const int64_t* index, int64_t n_kept,
+                           const int64_t* n_kept_dev, int64_t partition_offset, double* out, uint64_t seed,
+                           void* stream);
 
 /* DPEngine.add_dp_noise (dp_engine.py:551-607): out[i] = the secure
  * mechanism `noise` applied to (double)values[i], the `lambda value:

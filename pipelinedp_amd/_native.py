@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PIPELINEDP_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "lib", "libpipelinedp_amd.so")
 
 # constants (include/pipelinedp_amd.h)
-ABI_VERSION = 14
+ABI_VERSION = 15
 VALUE_NONE, VALUE_F64, VALUE_I64 = 0, 1, 2
 ACC_SUM, ACC_NSUM, ACC_NSUM2, SUM_PER_PARTITION, SUM_INT = 0x1, 0x2, 0x4, 0x8, 0x10
 DEBUG_CORRUPT_RECORDS = 0x40000000  # tests only (pipelinedp_amd.h)
@@ -36,6 +36,9 @@ MAX_L0 = 2**31 - 1            # pipelinedp_amd.h PDP_MAX_*
 MAX_LINF = 2**31 - 1
 MAX_CONTRIBUTIONS = 2**31 - 1
 MAX_OPS = 8
+MAX_VECTOR_SIZE = 4096      # PDP_MAX_VECTOR_SIZE
+NORM_LINF, NORM_L1, NORM_L2 = 0, 1, 2
+VECTOR_SUM_SLOT = 0x56454353  # Philox slot of the vector-sum noise ("VECS")
 
 EXPORTED_SYMBOLS = (
     "pdp_abi_version",
@@ -49,6 +52,9 @@ EXPORTED_SYMBOLS = (
     "pdp_compact",
     "pdp_noise_metrics",
     "pdp_add_noise",
+    "pdp_vector_sum_workspace_bytes",
+    "pdp_reduce_vector_sum",
+    "pdp_vector_sum_metrics",
     "pdp_dataset_histograms_workspace_bytes",
     "pdp_dataset_histograms",
     "pdp_dataset_histograms_pairs",
@@ -233,6 +239,10 @@ def signatures():
         "pdp_noise_metrics": (ctypes.c_int, [P(MetricOp), i32, vp, i64, vp, i64,
                                              P(PartitionAccumulators), i32, vp, vp, i64, u64, vp]),
         "pdp_add_noise": (ctypes.c_int, [vp, i32, i64, P(NoiseParams), u64, i64, vp, vp]),
+        "pdp_vector_sum_workspace_bytes": (ctypes.c_int, [P(BoundConfig), i32, P(u64)]),
+        "pdp_reduce_vector_sum": (ctypes.c_int, [P(BoundConfig), vp, vp, vp, vp, i32, vp, u64, vp, vp]),
+        "pdp_vector_sum_metrics": (ctypes.c_int, [vp, i32, i32, ctypes.c_double, P(NoiseParams), vp, i64, vp,
+                                                  i64, vp, u64, vp]),
         "pdp_dataset_histograms_workspace_bytes": (ctypes.c_int, [i64, i64, i64, P(u64)]),
         "pdp_dataset_histograms": (ctypes.c_int, [vp, vp, vp, i32, i64, i64, i64, P(HistogramBins),
                                                   vp, u64, vp]),

@@ -153,6 +153,8 @@ class ColumnTable:
     def _item(self, key, i):
         c = self._cols[key]
         v = c[i]
+        if getattr(v, "ndim", 0) > 0:  # a row of a 2-D column (VECTOR_SUM): the vector
+            return v.cpu().numpy() if _is_torch(v) else np.asarray(v)
         return v.item() if hasattr(v, "item") else v
 
     def __iter__(self):
@@ -235,7 +237,8 @@ class AggregateResult(Sequence):
 
     Nothing is built per partition until an element is read:
     `partition_keys` (a NumPy array) and `columns` (field name -> float64
-    NumPy array, the MetricsTuple field order) are the materialised result;
+    NumPy array, the MetricsTuple field order; `vector_sum` is 2-D, one row of
+    vector_size coordinates per partition) are the materialised result;
     indexing / iterating yields the reference's tuples on demand.  Partitions
     come in ascending partition-code order (the reference's LocalBackend
     yields first-appearance order; compare by key)."""
@@ -254,7 +257,7 @@ class AggregateResult(Sequence):
         return len(self.partition_keys)
 
     def _row(self, i):
-        return (_py_key(self.partition_keys[i]), self._nt(*(float(self.columns[f][i]) for f in self._fields)))
+        return (_py_key(self.partition_keys[i]), self._nt(*(_field(self.columns[f], i) for f in self._fields)))
 
     def __getitem__(self, i):
         if isinstance(i, slice):
@@ -266,7 +269,8 @@ class AggregateResult(Sequence):
         return self._row(i)
 
     def __iter__(self):
-        cols = [self.columns[f].tolist() for f in self._fields]
+        cols = [self.columns[f].tolist() if self.columns[f].ndim == 1 else list(self.columns[f])
+                for f in self._fields]
         keys = self.partition_keys.tolist()
         nt = self._nt
         return (( k, nt(*vals)) for k, *vals in zip(keys, *cols))
@@ -278,10 +282,17 @@ class AggregateResult(Sequence):
         """pyarrow Table (partition_key + one column per metric)."""
         import pyarrow as pa
         return pa.table({"partition_key": pa.array(self.partition_keys.tolist()),
-                         **{f: pa.array(v) for f, v in self.columns.items()}})
+                         **{f: pa.array(v) if v.ndim == 1 else
+                            pa.FixedSizeListArray.from_arrays(pa.array(v.ravel()), v.shape[1])
+                            for f, v in self.columns.items()}})
 
     def __repr__(self):
         return f"AggregateResult({len(self)} partitions, fields={self._fields})"
+
+
+def _field(col, i):
+    """Field i of a metric column: a float, or the vector of a 2-D column."""
+    return float(col[i]) if col.ndim == 1 else col[i].copy()
 
 
 def _py_key(k):

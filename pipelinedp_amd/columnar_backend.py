@@ -329,6 +329,24 @@ class MetricsProgram:
         self.int_bounds = True
         self.needs_values = False
         self.threshold_combiner = None
+        self.vector = None       # VectorSumCombiner: VectorProgram (its field comes last)
+
+    @property
+    def all_fields(self):
+        return self.fields + (["vector_sum"] if self.vector is not None else [])
+
+
+class VectorProgram:
+    """pdp_vector_sum_metrics arguments of a VectorSumCombiner."""
+
+    def __init__(self, size, norm_kind, max_norm, noise):
+        self.size = int(size)
+        self.norm_kind = norm_kind   # N.NORM_*
+        self.max_norm = float(max_norm)
+        self.noise = noise           # dpc.NoiseParams, per coordinate
+
+
+_NORM_CODES = {"linf": N.NORM_LINF, "l1": N.NORM_L1, "l2": N.NORM_L2}
 
 
 def _noise_kind_code(kind) -> int:
@@ -406,9 +424,25 @@ def build_metrics_program(compound, params) -> MetricsProgram:
                                          min_value=float(lo),
                                          sq_min_value=float(dpc.compute_squares_interval(lo, hi)[0]),
                                          degenerate=int(lo == hi)))
+        elif name == "VectorSumCombiner":
+            p = c._params.aggregate_params
+            if not 1 <= int(p.vector_size) <= N.MAX_VECTOR_SIZE:
+                raise NotImplementedError(f"vector_size={p.vector_size} is outside the supported range "
+                                          f"[1, {N.MAX_VECTOR_SIZE}]")
+            norm = _enum_value(p.vector_norm_kind)
+            if norm not in _NORM_CODES:
+                raise NotImplementedError(f"Vector Norm of kind '{norm}' is not supported.")
+            # add_noise_vector (dp_computations.py:212-229): eps / d and delta / d per
+            # coordinate, sensitivities = the L0 / Linf contribution bounds
+            noise = dpc.noise_params(_to_local_noise_kind(p.noise_kind), c._params.eps / p.vector_size,
+                                     c._params.delta / p.vector_size, p.max_partitions_contributed,
+                                     p.max_contributions_per_partition)
+            prog.vector = VectorProgram(p.vector_size, _NORM_CODES[norm], p.vector_max_norm, noise)
         else:
             raise NotImplementedError(f"{name} is not supported by ColumnarBackend "
-                                      "(hot path: Count/Sum/Mean/Variance/PrivacyIdCount)")
+                                      "(hot path: Count/Sum/Mean/Variance/PrivacyIdCount/VectorSum)")
+    if prog.vector is not None and prog.needs_values:
+        raise NotImplementedError("VECTOR_SUM cannot be combined with scalar value metrics")
     return prog
 
 
@@ -623,7 +657,7 @@ class AggregateRun:
             rows = [self.plan.extract_fn(r) for r in src]
             pid_raw = [r[0] for r in rows]
             pk_raw = [r[1] for r in rows]
-            val_raw = [r[2] for r in rows] if self.prog.needs_values else None
+            val_raw = [r[2] for r in rows] if self.prog.needs_values or self.prog.vector is not None else None
             n_pid = n_pk = None
             pk_decode = None
         units = self.plan.bounder == "already_enforced"  # no privacy ids on this path
@@ -648,7 +682,14 @@ class AggregateRun:
         pk_t = _h2d(pk_enc.codes, device, torch.int64)
         val_t = None
         value_kind = N.VALUE_NONE
-        if self.prog.needs_values:
+        if self.prog.vector is not None:
+            if parallel.world_info()[0] > 1:
+                raise NotImplementedError("VECTOR_SUM runs on one GPU: the exchange of the "
+                                          "[partitions, vector_size] accumulator across ranks is not implemented")
+            if val_raw is None:
+                raise ValueError("the value extractor must return the vector column for VECTOR_SUM")
+            val_t = _vector_tensor(val_raw, self.prog.vector.size, device)
+        elif self.prog.needs_values:
             if val_raw is None:
                 raise ValueError("the value extractor must return a value column for SUM/MEAN/VARIANCE")
             val_t = _value_tensor(val_raw, device)
@@ -701,7 +742,17 @@ class AggregateRun:
             allowed = torch.as_tensor(mask).to(pk_t.device)
         seed_bound, _, _ = self._seeds
         n_pid = 1 if pid_enc is None else pid_enc.n
-        if pk_t.numel() == 0:
+        self._vector_acc = None
+        if self.prog.vector is not None:
+            # the values never pass through the pair table: bounding sees no value column
+            if self.backend._workspace is None:
+                self.backend._workspace = X.BoundWorkspace()
+            acc, self._vector_acc = X.reduce_vector_sum(
+                pid_t, pk_t, val_t, n_privacy_ids=n_pid, n_partitions=P, bounding=spec, seed=seed_bound,
+                allowed=allowed, row_offset=row_offset, workspace=self.backend._workspace, check_keys="defer")
+            self.backend.last_plan_info = X.bound_plan(pk_t.numel(), n_pid, P, spec, algorithm=N.ALGO_PAIR_TABLE)
+            self.backend.last_bounding = spec
+        elif pk_t.numel() == 0:
             acc = X.new_accumulators(P, spec, pk_t.device)
         else:
             if self.backend._workspace is None:
@@ -759,6 +810,12 @@ class AggregateRun:
                                                     n_cols=len(self.prog.fields), seed_select=seed_select,
                                                     seed_noise=seed_noise, public_mask=public_mask,
                                                     partition_offset=first, sync_count=False)
+        vout = None
+        if self.prog.vector is not None:  # VectorSumCombiner.compute_metrics of the kept partitions
+            v = self.prog.vector
+            vout = X.vector_sum_metrics(self._vector_acc, index, norm_kind=v.norm_kind, max_norm=v.max_norm,
+                                        noise=v.noise, seed=seed_noise, n_kept_dev=n_kept_dev,
+                                        partition_offset=first)
         # the kept count and the kept columns in one round trip (one stream sync)
         idx, vals, n_kept = X.kept_to_host_guess(index, out, n_kept_dev, keys_only=self.plan.keys_only,
                                                  key=(int(index.shape[0]), len(self.prog.fields),
@@ -772,8 +829,10 @@ class AggregateRun:
         keep = np.ones(len(idx), dtype=bool)
         if self.prog.threshold_combiner is not None:  # dp_engine.py:544-549: drop thresholded None (NaN)
             keep = ~np.isnan(vals[self.prog.fields.index("privacy_id_count")])
-        nt = pdc._get_or_create_named_tuple("MetricsTuple", tuple(self.prog.fields))
+        nt = pdc._get_or_create_named_tuple("MetricsTuple", tuple(self.prog.all_fields))
         cols = {f: np.ascontiguousarray(vals[c][keep]) for c, f in enumerate(self.prog.fields)}
+        if vout is not None:  # [kept, vector_size]: one np.ndarray per partition
+            cols["vector_sum"] = np.ascontiguousarray(vout[:n_kept].cpu().numpy()[keep])
         return C.AggregateResult(pk_enc.keys_of(first + idx[keep]), cols, nt)
 
     def raw_accumulators(self):
@@ -781,6 +840,7 @@ class AggregateRun:
         host = {k: (None if v is None else v.cpu().numpy()) for k, v in acc.items()}
         self._raise_key_errors()
         public = allowed.cpu().numpy().astype(bool) if allowed is not None else None
+        vhost = None if self._vector_acc is None else self._vector_acc.cpu().numpy()
         out = {}
         for p in range(pk_enc.n):
             rc = int(host["privacy_id_count"][p])
@@ -803,6 +863,8 @@ class AggregateRun:
                 elif name == "VarianceCombiner":
                     children.append((int(host["count"][p]), float(host["normalized_sum"][p]),
                                      float(host["normalized_sum_sq"][p])))
+                elif name == "VectorSumCombiner":
+                    children.append(vhost[p].copy())
             row_count = rc + (1 if public is not None else 0)  # empty public accumulator
             out[pk_enc.key_of(p)] = (row_count, tuple(children))
         return out
@@ -877,6 +939,29 @@ def _host_or_device(col):
     if C._is_torch(col) or isinstance(col, C.DictColumn):
         return col
     return np.asarray(col) if not isinstance(col, np.ndarray) else col
+
+
+def _vector_tensor(col, size, device):
+    """The VECTOR_SUM value column as a float64 [n, size] device tensor: a 2-D
+    array / tensor as it is, else the rows' arrays or lists stacked.  A row
+    whose shape is not (size,) raises the reference's TypeError
+    (VectorSumCombiner.create_accumulator, combiners.py:815-820)."""
+    import torch
+    if C._is_torch(col) or (isinstance(col, np.ndarray) and col.dtype != object):
+        if col.ndim != 2 or col.shape[1] != size:
+            raise TypeError(f"Shape mismatch: {tuple(col.shape[1:])} != {(size,)}")
+        if C._is_torch(col):
+            return col.to(device=device, dtype=torch.float64).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(col, dtype=np.float64)).to(device)
+    rows = []
+    for val in col:
+        if not isinstance(val, np.ndarray):
+            val = np.array(val)
+        if val.shape != (size,):
+            raise TypeError(f"Shape mismatch: {val.shape} != {(size,)}")
+        rows.append(val)
+    arr = np.stack(rows).astype(np.float64) if rows else np.zeros((0, size))
+    return torch.as_tensor(arr).to(device)
 
 
 def _value_tensor(col, device):

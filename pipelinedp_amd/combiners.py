@@ -6,7 +6,9 @@ Each combiner keeps the reference's accumulator definition
 ColumnarBackend these methods are never called per row: the backend reads
 the combiner's configuration (bounds, mechanism specs, metric names) and runs
 the same arithmetic in the HIP kernels (csrc/pdp_bound.hip, pdp_select.hip).
-Quantile, vector-sum and custom combiners are outside the hot path.
+VectorSumCombiner's accumulator and metrics run in pdp_pairs.hip /
+pdp_select.hip (pdp_reduce_vector_sum, pdp_vector_sum_metrics).  Quantile and
+custom combiners are outside the hot path.
 """
 import abc
 import collections
@@ -84,6 +86,15 @@ class CombinerParams:
                                      p.min_sum_per_partition, p.max_sum_per_partition,
                                      p.max_partitions_contributed, p.max_contributions_per_partition,
                                      p.noise_kind)
+
+    @property
+    def additive_vector_noise_params(self) -> dpc.AdditiveVectorNoiseParams:
+        p = self.aggregate_params
+        return dpc.AdditiveVectorNoiseParams(
+            eps_per_coordinate=self.eps / p.vector_size, delta_per_coordinate=self.delta / p.vector_size,
+            max_norm=p.vector_max_norm, l0_sensitivity=p.max_partitions_contributed,
+            linf_sensitivity=p.max_contributions_per_partition, norm_kind=p.vector_norm_kind,
+            noise_kind=p.noise_kind)
 
 
 class MechanismContainerMixin(abc.ABC):
@@ -364,6 +375,45 @@ class VarianceCombiner(Combiner):
         return self._params.mechanism_spec
 
 
+class VectorSumCombiner(Combiner):
+    """Accumulator: the np.ndarray sum of the values' vectors, each of shape
+    (vector_size,), without per-row clipping; the partition's total is clipped
+    to vector_max_norm and noised per coordinate (reference :800-847)."""
+
+    def __init__(self, params: CombinerParams):
+        self._params = params
+
+    @property
+    def params(self) -> CombinerParams:
+        return self._params
+
+    def create_accumulator(self, values):
+        size = self._params.aggregate_params.vector_size
+        array_sum = None
+        for val in values:
+            if not isinstance(val, np.ndarray):
+                val = np.array(val)
+            if val.shape != (size,):
+                raise TypeError(f"Shape mismatch: {val.shape} != {(size,)}")
+            array_sum = val.copy() if array_sum is None else array_sum + val
+        return array_sum
+
+    def merge_accumulators(self, array_sum1, array_sum2):
+        return array_sum1 + array_sum2
+
+    def compute_metrics(self, array_sum) -> dict:
+        return {"vector_sum": dpc.add_noise_vector(array_sum, self._params.additive_vector_noise_params)}
+
+    def metrics_names(self) -> List[str]:
+        return ["vector_sum"]
+
+    def explain_computation(self):
+        return lambda: f"Computed vector sum with (eps={self._params.eps} delta={self._params.delta})"
+
+    def mechanism_spec(self):
+        return self._params.mechanism_spec
+
+
 def variance_noise_scales(dp_params: dpc.ScalarNoiseParams):
     """Noise scales of compute_dp_var's three mechanisms (reference
     dp_computations.py:306-365): count, normalised sum, normalised sum of
@@ -490,7 +540,7 @@ class CompoundCombiner(Combiner):
 def create_compound_combiner(aggregate_params: agg.AggregateParams,
                              budget_accountant) -> CompoundCombiner:
     """Combiner set and budget-request order of the reference (:849-922):
-    VARIANCE > MEAN > {COUNT, SUM}, then PRIVACY_ID_COUNT."""
+    VARIANCE > MEAN > {COUNT, SUM}, then PRIVACY_ID_COUNT, then VECTOR_SUM."""
     metrics = aggregate_params.metrics
     mechanism_type = aggregate_params.noise_kind.convert_to_mechanism_type()
     weight = aggregate_params.budget_weight
@@ -520,7 +570,8 @@ def create_compound_combiner(aggregate_params: agg.AggregateParams,
             combiners.append(PrivacyIdCountCombiner(
                 budget_accountant.request_budget(mechanism_type, weight=weight), aggregate_params))
     if agg.Metrics.VECTOR_SUM in metrics:
-        raise NotImplementedError("VECTOR_SUM is not on the pipelinedp_amd hot path")
+        budget = budget_accountant.request_budget(mechanism_type, weight=weight)
+        combiners.append(VectorSumCombiner(CombinerParams(budget, aggregate_params)))
     if any(m.is_percentile for m in metrics):
         raise NotImplementedError("PERCENTILE (PyDP quantile trees) is not on the pipelinedp_amd hot path")
     return CompoundCombiner(combiners, return_named_tuple=True)

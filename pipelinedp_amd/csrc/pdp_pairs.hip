@@ -700,7 +700,323 @@ struct RunUnits {
   }
 };
 
+// ------------------------------------------------------------ VECTOR_SUM --
+// VectorSumCombiner's accumulator (combiners.py:800-830): per partition the
+// sum of the kept rows' vectors.  The pair table above already encodes which
+// rows the bounder keeps, so the values never pass through it:
+//   k_vs_mark     one pass over the key columns: mark[i] = partition of a kept
+//                 row (else ~0), and rows per partition
+//   scan_u32      -> segment offsets; k_vs_scatter: kept row indices by partition
+//   k_vs_reduce   one wave per work item, lanes across coordinates (8 or 16 B
+//                 per lane), 64 / lanes-per-row rows in flight.  Items: every
+//                 partition with <= kVsTile kept rows (summed whole, added to
+//                 the caller's accumulator by its only writer), and every tile
+//                 of kVsTile consecutive entries of the kept-row list, which
+//                 sums the pieces of the (at most two) longer partitions it
+//                 overlaps into partial[tile][0 | 1]
+//   k_vs_combine  one wave per longer partition adds its tiles' partials
+// No atomic touches a double: a hot partition is split over the tiles' waves.
+constexpr unsigned kVsTile = 1024;
+constexpr unsigned kVsNone = ~0u;
+
+struct VWs {
+  uint64_t mark, rows, pcnt, pcur, chunks, partial, total;
+};
+
+__host__ __device__ inline int64_t vs_tiles(int64_t n) { return (n + kVsTile - 1) / kVsTile; }
+
+VWs vlayout(const pdp_bound_config* c, int d) {
+  VWs v{};
+  const uint64_t n = (uint64_t)c->n_rows, P = (uint64_t)c->n_partitions;
+  uint64_t off = align256(playout(c).total);
+  v.mark = off; off = align256(off + n * 4);
+  v.rows = off; off = align256(off + n * 4);
+  v.pcnt = off; off = align256(off + (P + 1) * 4);
+  v.pcur = off; off = align256(off + P * 4);
+  v.chunks = off; off = align256(off + (uint64_t)scan_chunk_sums_len((int64_t)P) * 4);
+  v.partial = off; off = align256(off + (uint64_t)vs_tiles(c->n_rows) * 2 * (uint64_t)d * 8);
+  v.total = off;
+  return v;
+}
+
+struct VsTab {
+  const unsigned* pid_cnt;
+  const unsigned* pid_off;
+  const unsigned long long* pid_pool;
+  const unsigned long long* keys;
+  const unsigned* cnt;
+  const unsigned* pair_off;
+  const unsigned long long* pair_pool;
+  const uint8_t* keep;
+};
+
+// table_find that also ends at a free slot (capacity >= 2 * rows: one exists),
+// so key columns other than the bounded ones cannot make it spin
+__device__ __forceinline__ bool table_lookup(const unsigned long long* keys, uint64_t mask, uint64_t x,
+                                             uint64_t* slot) {
+  uint64_t h = slot_hash(x, mask);
+  for (;;) {
+    const unsigned long long cur = keys[h];
+    if (cur == x) {
+      *slot = h;
+      return true;
+    }
+    if (cur == kEmpty) return false;
+    h = (h + 1) & mask;
+  }
+}
+
+// Is row i one of the rows whose pair accumulators pairs_bound built?
+__device__ __forceinline__ bool vs_row_kept(const PT& t, const VsTab& tb, const int64_t* __restrict__ pid,
+                                            const int64_t* __restrict__ pk, const uint8_t* __restrict__ allowed,
+                                            int64_t i, int64_t* k, unsigned* err) {
+  int64_t u;
+  if (!row_ok(t, pid, pk, allowed, i, &u, k, err)) return false;
+  if (tb.keys == nullptr) return true;  // rows_are_units
+  if (!pid_keeps(t, tb.pid_cnt, tb.pid_off, tb.pid_pool, u, i)) return false;
+  if (t.l0 <= 0 && t.linf <= 0) return true;
+  uint64_t slot;
+  if (!table_lookup(tb.keys, t.mask, ((uint64_t)u << t.pk_bits) | (uint64_t)*k, &slot)) return false;
+  if (tb.keep != nullptr && tb.keep[slot] == 0) return false;
+  if (t.linf <= 0 || tb.cnt[slot] <= (unsigned)t.linf) return true;
+  const uint64_t y = row_key(t.row_seed, t.row_offset + i, (uint32_t)i);
+  return y <= tb.pair_pool[(uint64_t)tb.pair_off[slot] + t.linf - 1];
+}
+
+__global__ void __launch_bounds__(kBlock) k_vs_mark(PT t, VsTab tb, const int64_t* __restrict__ pid,
+                                                    const int64_t* __restrict__ pk,
+                                                    const uint8_t* __restrict__ allowed, unsigned* mark,
+                                                    unsigned* pcnt, unsigned* err) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
+    int64_t k;
+    const bool kept = vs_row_kept(t, tb, pid, pk, allowed, i, &k, err);
+    mark[i] = kept ? (unsigned)k : kVsNone;
+    if (kept) atomicAdd(pcnt + k, 1u);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_vs_scatter(int64_t n, int64_t P, const unsigned* __restrict__ mark,
+                                                       const unsigned* __restrict__ poff, unsigned* pcur,
+                                                       unsigned* rows) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned k = mark[i];
+    if (k == kVsNone || (int64_t)k >= P) continue;
+    const uint64_t at = (uint64_t)poff[k] + atomicAdd(pcur + k, 1u);
+    if (at < (uint64_t)n) rows[at] = (unsigned)i;
+  }
+}
+
+// V doubles per lane
+template <int V>
+struct VsVal {
+  double x[V];
+};
+
+template <int V>
+__device__ __forceinline__ VsVal<V> vs_load(const double* p) {
+  VsVal<V> r;
+  if constexpr (V == 2) {
+    const double2 q = *reinterpret_cast<const double2*>(p);
+    r.x[0] = q.x;
+    r.x[1] = q.y;
+  } else {
+    r.x[0] = *p;
+  }
+  return r;
+}
+
+template <int V>
+__device__ __forceinline__ void vs_store(double* p, const VsVal<V>& v, bool add) {
+  if constexpr (V == 2) {
+    double2 q = add ? *reinterpret_cast<const double2*>(p) : make_double2(0.0, 0.0);
+    q.x += v.x[0];
+    q.y += v.x[1];
+    *reinterpret_cast<double2*>(p) = q;
+  } else {
+    *p = (add ? *p : 0.0) + v.x[0];
+  }
+}
+
+// The wave's sum over entries [a, b) of `src` rows (row of entry r:
+// rows ? rows[r] : r), each `ld` doubles long, of this lane's coordinates
+// [col * V, col * V + V): slot s of the 64 >> log2_g row slots takes entries
+// a + s, a + s + R, ...; then the slots are folded with wave shuffles, so
+// every slot's lanes hold the total.  Every lane of the wave calls it.
+template <int V>
+__device__ __forceinline__ VsVal<V> vs_sum(const double* __restrict__ src, const unsigned* __restrict__ rows,
+                                           uint64_t ld, uint64_t a, uint64_t b, int slot, int log2_g, int64_t col,
+                                           bool active) {
+  const uint64_t R = 64u >> log2_g;
+  VsVal<V> s;
+  for (int q = 0; q < V; ++q) s.x[q] = 0.0;
+  if (active) {
+    const double* base = src + col * V;
+    uint64_t r = a + (uint64_t)slot;
+    for (; r + 3 * R < b; r += 4 * R) {  // four rows of this slot in flight
+      const uint64_t i0 = rows ? rows[r] : r, i1 = rows ? rows[r + R] : r + R;
+      const uint64_t i2 = rows ? rows[r + 2 * R] : r + 2 * R, i3 = rows ? rows[r + 3 * R] : r + 3 * R;
+      const VsVal<V> v0 = vs_load<V>(base + i0 * ld), v1 = vs_load<V>(base + i1 * ld);
+      const VsVal<V> v2 = vs_load<V>(base + i2 * ld), v3 = vs_load<V>(base + i3 * ld);
+      for (int q = 0; q < V; ++q) s.x[q] += (v0.x[q] + v1.x[q]) + (v2.x[q] + v3.x[q]);
+    }
+    for (; r < b; r += R) {
+      const VsVal<V> v = vs_load<V>(base + (rows ? (uint64_t)rows[r] : r) * ld);
+      for (int q = 0; q < V; ++q) s.x[q] += v.x[q];
+    }
+  }
+  for (int o = 1 << log2_g; o < 64; o <<= 1)
+    for (int q = 0; q < V; ++q) s.x[q] += __shfl_xor(s.x[q], o, 64);
+  return s;
+}
+
+// partition holding entry r of the kept-row list: the p with off[p] <= r < off[p + 1]
+// (r < off[P]; off is non-decreasing with off[0] = 0)
+__device__ __forceinline__ int64_t vs_partition_of(const unsigned* __restrict__ off, int64_t P, uint64_t r) {
+  int64_t lo = 0, hi = P;  // smallest q in [1, P] with off[q] > r
+  while (lo + 1 < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)off[mid] > r) hi = mid; else lo = mid;
+  }
+  return hi - 1;
+}
+
+struct VsGeom {
+  int d;        // vector_size
+  int cols;     // d / V lane columns
+  int log2_g;   // lanes per row = 2^log2_g (64: column chunk blockIdx.y of 64 columns)
+};
+
+template <int V>
+__global__ void __launch_bounds__(kBlock) k_vs_reduce(VsGeom g, int64_t n, int64_t P,
+                                                      const double* __restrict__ vectors,
+                                                      const unsigned* __restrict__ rows,
+                                                      const unsigned* __restrict__ off, double* acc,
+                                                      double* partial) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int slot = lane >> g.log2_g;
+  const int64_t col = (int64_t)(lane & ((1 << g.log2_g) - 1)) + (int64_t)blockIdx.y * 64;
+  const bool active = col < g.cols;
+  const uint64_t total = off[P];
+  const int64_t tiles = vs_tiles(n), items = P + tiles;
+  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t it = (int64_t)blockIdx.x * (kBlock / 64) + wave; it < items; it += wstride) {
+    if (it < P) {  // a partition of at most kVsTile kept rows, whole
+      const uint64_t a = off[it], b = off[it + 1];
+      if (b <= a || b - a > kVsTile || b > total) continue;
+      const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, a, b, slot, g.log2_g, col, active);
+      if (slot == 0 && active) vs_store<V>(acc + (uint64_t)it * g.d + col * V, s, true);
+      continue;
+    }
+    const uint64_t tile = (uint64_t)(it - P);
+    const uint64_t r0 = tile * kVsTile;
+    if (r0 >= total) continue;
+    const uint64_t r1 = r0 + kVsTile < total ? r0 + kVsTile : total;
+    const int64_t pf = vs_partition_of(off, P, r0), pl = vs_partition_of(off, P, r1 - 1);
+    if (off[pf + 1] - off[pf] > kVsTile) {
+      const uint64_t e = off[pf + 1] < r1 ? off[pf + 1] : r1;
+      const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, r0, e, slot, g.log2_g, col, active);
+      if (slot == 0 && active) vs_store<V>(partial + (tile * 2) * g.d + col * V, s, false);
+    }
+    if (pl != pf && off[pl + 1] - off[pl] > kVsTile) {
+      const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, off[pl], r1, slot, g.log2_g, col, active);
+      if (slot == 0 && active) vs_store<V>(partial + (tile * 2 + 1) * g.d + col * V, s, false);
+    }
+  }
+}
+
+// partitions of more than kVsTile kept rows: tile t holds the partition's piece
+// in partial[t][0] if the partition owns the tile's first entry, else in [t][1]
+// (only its first tile can)
+template <int V>
+__global__ void __launch_bounds__(kBlock) k_vs_combine(VsGeom g, int64_t P, const unsigned* __restrict__ off,
+                                                       const double* __restrict__ partial, double* acc) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int slot = lane >> g.log2_g;
+  const int64_t col = (int64_t)(lane & ((1 << g.log2_g) - 1)) + (int64_t)blockIdx.y * 64;
+  const bool active = col < g.cols;
+  const uint64_t total = off[P];
+  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t p = (int64_t)blockIdx.x * (kBlock / 64) + wave; p < P; p += wstride) {
+    const uint64_t a = off[p], b = off[p + 1];
+    if (b <= a || b - a <= kVsTile || b > total) continue;
+    const uint64_t t0 = a / kVsTile, t1 = (b - 1) / kVsTile;
+    VsVal<V> s;
+    if (a == t0 * kVsTile) {  // every piece in slot [t][0]: rows of 2 d doubles
+      s = vs_sum<V>(partial, nullptr, 2 * (uint64_t)g.d, t0, t1 + 1, slot, g.log2_g, col, active);
+    } else {
+      s = vs_sum<V>(partial, nullptr, 2 * (uint64_t)g.d, t0 + 1, t1 + 1, slot, g.log2_g, col, active);
+      if (active) {
+        const VsVal<V> f = vs_load<V>(partial + (t0 * 2 + 1) * g.d + col * V);
+        for (int q = 0; q < V; ++q) s.x[q] += f.x[q];
+      }
+    }
+    if (slot == 0 && active) vs_store<V>(acc + (uint64_t)p * g.d + col * V, s, true);
+  }
+}
+
+template <int V>
+int launch_vs(const VsGeom& g, int64_t n, int64_t P, const double* vectors, const unsigned* rows,
+              const unsigned* off, double* acc, double* partial, hipStream_t st) {
+  const unsigned gy = g.log2_g == 6 ? (unsigned)((g.cols + 63) / 64) : 1u;
+  const int64_t items = P + vs_tiles(n);
+  const unsigned gx = grid_for(items * 64, 8192);
+  PDP_LAUNCH("k_vs_reduce", st, k_vs_reduce<V>, dim3(gx, gy), dim3(kBlock), 0, st, g, n, P, vectors, rows, off, acc,
+             partial);
+  const unsigned gp = grid_for(P * 64, 8192);
+  PDP_LAUNCH("k_vs_combine", st, k_vs_combine<V>, dim3(gp, gy), dim3(kBlock), 0, st, g, P, off, partial, acc);
+  return PDP_OK;
+}
+
 }  // namespace
+
+uint64_t pairs_vector_workspace_bytes(const pdp_bound_config* c, int vector_size) {
+  return vlayout(c, vector_size).total;
+}
+
+int pairs_vector_sum(const pdp_bound_config* c, const int64_t* pid, const int64_t* pk, const uint8_t* allowed,
+                     const double* vectors, int d, char* ws, double* vector_acc, hipStream_t st) {
+  const PWs w = playout(c);
+  const VWs v = vlayout(c, d);
+  const PT t = make_pt(c);
+  const int64_t n = c->n_rows, P = c->n_partitions;
+  if (n == 0) return PDP_OK;
+  unsigned* pcnt = (unsigned*)(ws + v.pcnt);
+  unsigned* pcur = (unsigned*)(ws + v.pcur);
+  unsigned* mark = (unsigned*)(ws + v.mark);
+  unsigned* rows = (unsigned*)(ws + v.rows);
+  PDP_HIP_CHECK(hipMemsetAsync(pcnt, 0, ((uint64_t)P + 1) * 4, st));
+  PDP_HIP_CHECK(hipMemsetAsync(pcur, 0, (uint64_t)P * 4, st));
+  VsTab tb{};
+  if (!c->rows_are_units) {
+    const bool per_pid = t.maxc > 0 || t.l0 > 0;
+    tb.pid_cnt = per_pid ? (const unsigned*)(ws + w.pid_cnt) : nullptr;
+    tb.pid_off = per_pid ? (const unsigned*)(ws + w.pid_off) : nullptr;
+    tb.pid_pool = per_pid ? (const unsigned long long*)(ws + w.pid_pool) : nullptr;
+    tb.keys = (const unsigned long long*)(ws + w.keys);
+    tb.cnt = (const unsigned*)(ws + w.cnt);
+    tb.pair_off = t.linf > 0 ? (const unsigned*)(ws + w.pair_off) : nullptr;
+    tb.pair_pool = t.linf > 0 ? (const unsigned long long*)(ws + w.pair_pool) : nullptr;
+    tb.keep = t.l0 > 0 ? (const uint8_t*)(ws + w.pkeep) : nullptr;
+  }
+  const unsigned g = grid_for(n);
+  PDP_LAUNCH("k_vs_mark", st, k_vs_mark, dim3(g), dim3(kBlock), 0, st, t, tb, c->rows_are_units ? nullptr : pid, pk,
+             allowed, mark, pcnt, (unsigned*)(ws + w.err));
+  const int rc = scan_u32(pcnt, P, (unsigned*)(ws + v.chunks), st);
+  if (rc != PDP_OK) return rc;
+  PDP_LAUNCH("k_vs_scatter", st, k_vs_scatter, dim3(g), dim3(kBlock), 0, st, n, P, mark, pcnt, pcur, rows);
+  double* partial = (double*)(ws + v.partial);
+  // 16 B per lane where every row and the accumulator rows are 16-byte aligned
+  const bool wide = d % 2 == 0 && ((((uintptr_t)vectors) | ((uintptr_t)vector_acc)) & 15) == 0;
+  VsGeom geo;
+  geo.d = d;
+  geo.cols = wide ? d / 2 : d;
+  geo.log2_g = 0;
+  while (geo.log2_g < 6 && (1 << geo.log2_g) < geo.cols) ++geo.log2_g;
+  return wide ? launch_vs<2>(geo, n, P, vectors, rows, pcnt, vector_acc, partial, st)
+              : launch_vs<1>(geo, n, P, vectors, rows, pcnt, vector_acc, partial, st);
+}
 
 int pairs_validate(const pdp_bound_config* c) {
   if (c->algorithm != PDP_ALGO_AUTO && c->algorithm != PDP_ALGO_PAIR_TABLE)
@@ -765,3 +1081,47 @@ int pairs_reduce(const pdp_bound_config* c, const void* value, char* ws, const p
 }
 
 }  // namespace pdp
+
+using namespace pdp;
+
+extern "C" {
+
+// cfg must resolve to the pair table (pdp_bound_plan validates it); d in range
+static int vector_sum_check(const pdp_bound_config* cfg, int32_t vector_size) {
+  pdp_bound_plan_info info;
+  const int rc = pdp_bound_plan(cfg, &info);
+  if (rc != PDP_OK) return rc;
+  if (info.algorithm != PDP_ALGO_PAIR_TABLE)
+    return set_error(PDP_E_UNSUPPORTED,
+                     "vector sums read the pair table: set pdp_bound_config.algorithm = PDP_ALGO_PAIR_TABLE");
+  if (vector_size < 1 || vector_size > PDP_MAX_VECTOR_SIZE)
+    return set_error(PDP_E_UNSUPPORTED, "vector_size outside [1, PDP_MAX_VECTOR_SIZE]");
+  return PDP_OK;
+}
+
+int pdp_vector_sum_workspace_bytes(const pdp_bound_config* cfg, int32_t vector_size, uint64_t* bytes) {
+  const int rc = vector_sum_check(cfg, vector_size);
+  if (rc != PDP_OK) return rc;
+  if (bytes == nullptr) return set_error(PDP_E_INVALID, "bytes is NULL");
+  *bytes = pairs_vector_workspace_bytes(cfg, vector_size);
+  return PDP_OK;
+}
+
+int pdp_reduce_vector_sum(const pdp_bound_config* cfg, const int64_t* privacy_id, const int64_t* partition_key,
+                          const uint8_t* pk_allowed, const double* vectors, int32_t vector_size, void* workspace,
+                          uint64_t workspace_bytes, double* vector_acc, void* stream) {
+  const int rc = vector_sum_check(cfg, vector_size);
+  if (rc != PDP_OK) return rc;
+  if (workspace == nullptr || workspace_bytes < pairs_vector_workspace_bytes(cfg, vector_size))
+    return set_error(PDP_E_WORKSPACE, "workspace too small (see pdp_vector_sum_workspace_bytes)");
+  if (vector_acc == nullptr) return set_error(PDP_E_INVALID, "vector_acc is NULL");
+  if (cfg->n_rows > 0 && (partition_key == nullptr || (privacy_id == nullptr && !cfg->rows_are_units)))
+    return set_error(PDP_E_INVALID, "key columns are NULL");
+  if (cfg->n_rows > 0 && vectors == nullptr) return set_error(PDP_E_INVALID, "vectors is NULL");
+  if ((((uintptr_t)vectors) | ((uintptr_t)vector_acc)) & 7)
+    return set_error(PDP_E_INVALID, "vectors and vector_acc must be 8-byte aligned");
+  return pairs_vector_sum(cfg, privacy_id, partition_key, pk_allowed, vectors, vector_size, (char*)workspace,
+                          vector_acc, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -384,6 +384,45 @@ __global__ void __launch_bounds__(kBlock) k_noise_metrics(OpsPack ops, int n_ops
   }
 }
 
+// VectorSumCombiner.compute_metrics: one wave per kept partition, lanes across
+// coordinates; the L1 / L2 norm by a wave reduction, then clip + noise
+constexpr uint32_t kVectorSumSlot = PDP_VECTOR_SUM_SLOT;
+
+__global__ void __launch_bounds__(kBlock) k_vector_sum_metrics(const double* __restrict__ vacc, int d, int norm_kind,
+                                                               double max_norm, pdp_noise_params np,
+                                                               const int64_t* __restrict__ index, int64_t n_kept,
+                                                               const int64_t* __restrict__ n_kept_dev,
+                                                               int64_t partition_offset, double* __restrict__ out,
+                                                               uint64_t seed) {
+  int64_t n = n_kept;
+  if (n_kept_dev != nullptr) {
+    const int64_t dv = *n_kept_dev;
+    n = dv < n ? dv : n;
+  }
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); i < n; i += wstride) {
+    const int64_t p = index[i];
+    const double* v = vacc + p * d;
+    double coef = 1.0;
+    if (norm_kind != PDP_NORM_LINF) {
+      double s = 0.0;
+      for (int j = lane; j < d; j += 64) {
+        const double x = v[j];
+        s += norm_kind == PDP_NORM_L1 ? fabs(x) : x * x;
+      }
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      const double norm = norm_kind == PDP_NORM_L1 ? s : sqrt(s);
+      coef = fmin(1.0, max_norm / norm);  // norm 0: inf (or NaN for max_norm 0) -> 1
+    }
+    for (int j = lane; j < d; j += 64) {
+      const double x = v[j];
+      const double c = norm_kind == PDP_NORM_LINF ? fmin(fmax(x, -max_norm), max_norm) : x * coef;
+      out[i * d + j] = secure_add_noise(np, c, seed, (partition_offset + p) * d + j, kVectorSumSlot);
+    }
+  }
+}
+
 }  // namespace
 }  // namespace pdp
 
@@ -540,6 +579,31 @@ int pdp_add_noise(const void* values, int32_t value_kind, int64_t n, const pdp_n
   else
     hipLaunchKernelGGL(k_add_noise<PDP_VALUE_F64>, dim3(grid_for(pairs)), dim3(kBlock), 0, st, values, n,
                        *noise, seed, index_offset, out);
+  PDP_PROF_END(st);
+  PDP_HIP_CHECK(hipGetLastError());
+  return PDP_OK;
+}
+
+int pdp_vector_sum_metrics(const double* vector_acc, int32_t vector_size, int32_t norm_kind, double max_norm,
+                           const pdp_noise_params* noise, const int64_t* index, int64_t n_kept,
+                           const int64_t* n_kept_dev, int64_t partition_offset, double* out, uint64_t seed,
+                           void* stream) {
+  if (vector_size < 1 || vector_size > PDP_MAX_VECTOR_SIZE)
+    return pdp::set_error(PDP_E_UNSUPPORTED, "vector_size outside [1, PDP_MAX_VECTOR_SIZE]");
+  if (norm_kind != PDP_NORM_LINF && norm_kind != PDP_NORM_L1 && norm_kind != PDP_NORM_L2)
+    return pdp::set_error(PDP_E_INVALID, "norm_kind must be PDP_NORM_LINF, _L1 or _L2");
+  if (!(max_norm >= 0.0)) return pdp::set_error(PDP_E_INVALID, "max_norm must be >= 0");
+  if (n_kept < 0) return pdp::set_error(PDP_E_INVALID, "n_kept must be >= 0");
+  const int rc = pdp::check_noise(noise);
+  if (rc != PDP_OK) return rc;
+  if (n_kept == 0) return PDP_OK;
+  if (vector_acc == nullptr || index == nullptr || out == nullptr)
+    return pdp::set_error(PDP_E_INVALID, "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(n_kept * 64, 2048);  // one wave per kept partition
+  PDP_PROF_BEGIN("k_vector_sum_metrics", st);
+  hipLaunchKernelGGL(k_vector_sum_metrics, dim3(grid), dim3(kBlock), 0, st, vector_acc, (int)vector_size,
+                     (int)norm_kind, max_norm, *noise, index, n_kept, n_kept_dev, partition_offset, out, seed);
   PDP_PROF_END(st);
   PDP_HIP_CHECK(hipGetLastError());
   return PDP_OK;

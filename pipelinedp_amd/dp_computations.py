@@ -567,6 +567,50 @@ def noise_scale(noise_kind: agg.NoiseKind, eps: float, delta: float, l0: float, 
     raise ValueError("Noise kind must be either Laplace or Gaussian.")
 
 
+# ------------------------------------------------------------------ vector sums --
+@dataclasses.dataclass
+class AdditiveVectorNoiseParams:
+    """dp_computations.py:186-194."""
+    eps_per_coordinate: float
+    delta_per_coordinate: float
+    max_norm: float
+    l0_sensitivity: float
+    linf_sensitivity: float
+    norm_kind: agg.NormKind
+    noise_kind: agg.NoiseKind
+
+
+def clip_vector(vec: np.ndarray, max_norm: float, norm_kind: agg.NormKind) -> np.ndarray:
+    """_clip_vector (dp_computations.py:197-209): Linf clips every coordinate
+    to [-max_norm, max_norm]; L1 / L2 scale the vector by
+    min(1, max_norm / norm), which is 1 for the zero vector."""
+    vec = np.asarray(vec)
+    kind = norm_kind.value
+    if kind == "linf":
+        return np.clip(vec, -max_norm, max_norm)
+    if kind in ("l1", "l2"):
+        norm = float(np.linalg.norm(vec, ord=int(kind[-1])))
+        ratio = max_norm / norm if norm != 0 else math.inf
+        return vec * min(1, ratio)
+    raise NotImplementedError(f"Vector Norm of kind '{kind}' is not supported.")
+
+
+def vector_noise_params(p: AdditiveVectorNoiseParams) -> NoiseParams:
+    """The per-coordinate secure sampler of add_noise_vector: the sensitivities
+    are the L0 / Linf contribution bounds, as the reference passes them."""
+    return noise_params(p.noise_kind, p.eps_per_coordinate, p.delta_per_coordinate, p.l0_sensitivity,
+                        p.linf_sensitivity)
+
+
+def add_noise_vector(vec: np.ndarray, noise_params_: AdditiveVectorNoiseParams) -> np.ndarray:
+    """add_noise_vector (dp_computations.py:212-229) on the host secure sampler:
+    clip, then independent noise on every coordinate."""
+    vec = clip_vector(vec, noise_params_.max_norm, noise_params_.norm_kind)
+    np_ = vector_noise_params(noise_params_)
+    smp = secure_sampler()
+    return np.array([smp.add_noise(np_, s) for s in vec])
+
+
 # ---------------------------------------------------------- partition selection --
 def adjusted_delta(delta: float, max_partitions_contributed: int) -> float:
     """Per-partition delta: 1 - (1 - delta)^(1/l0), computed stably.

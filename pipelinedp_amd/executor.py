@@ -611,6 +611,113 @@ def bound_and_reduce(pid, pk, value, *, n_privacy_ids: int, n_partitions: int,
     return acc
 
 
+def _check_matrix(t, name, rows, cols, device):
+    """_check_col for a row-major float64 [rows, cols] device matrix."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor on the GPU")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name} has dtype {t.dtype}, expected torch.float64")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, expected {device}")
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != cols:
+        raise ValueError(f"{name} must be 2-D of shape ({rows}, {cols}), got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (row-major)")
+
+
+def reduce_vector_sum(pid, pk, vectors, *, n_privacy_ids: int, n_partitions: int, bounding: BoundingSpec,
+                      seed: int, row_offset: int = 0, allowed=None, acc=None, vector_acc=None,
+                      workspace: Optional[BoundWorkspace] = None, stream=None, check_keys=True,
+                      algorithm: int = N.ALGO_PAIR_TABLE):
+    """VECTOR_SUM's bounding + reduction of one shard: bounds the contributions
+    on the pair table (`pdp_bound_contributions`; `bounding`'s l0 / linf /
+    max_contributions / rows_are_units, no scalar value column), ADDS the
+    row / privacy-id counts to `acc` (`pdp_reduce_partitions`) and the kept
+    rows' vectors to `vector_acc` (`pdp_reduce_vector_sum`).
+
+    vectors: float64 device tensor [n, vector_size], row-major; vector_acc:
+    float64 [n_partitions, vector_size] (created zeroed when None).  Returns
+    (acc, vector_acc)."""
+    torch = _torch()
+    lib = N.lib()
+    device = pk.device
+    n = int(pk.shape[0])
+    if pid is None and not bounding.rows_are_units:
+        raise ValueError("privacy_id is required unless contribution bounds are already enforced")
+    if pid is not None:
+        _check_col(pid, "privacy_id", (torch.int64,), n, device)
+    _check_col(pk, "partition_key", (torch.int64,), n, device)
+    if not isinstance(vectors, torch.Tensor) or vectors.dim() != 2:
+        raise TypeError("vectors must be a 2-D torch tensor [n_rows, vector_size] on the GPU")
+    d = int(vectors.shape[1])
+    _check_matrix(vectors, "vectors", n, d, device)
+    if allowed is not None:
+        _check_col(allowed, "pk_allowed", (torch.uint8,), int(n_partitions), device)
+    if vector_acc is None:
+        vector_acc = torch.zeros((int(n_partitions), d), dtype=torch.float64, device=device)
+    _check_matrix(vector_acc, "vector_acc", int(n_partitions), d, device)
+    counts = dataclasses.replace(bounding, value_kind=N.VALUE_NONE, flags=0)
+    cfg = bound_config(n, n_privacy_ids, n_partitions, counts, seed, row_offset, algorithm)
+    nbytes = ctypes.c_uint64(0)
+    N.check(lib.pdp_vector_sum_workspace_bytes(ctypes.byref(cfg), d, ctypes.byref(nbytes)),
+            "pdp_vector_sum_workspace_bytes")
+    wsobj = workspace or BoundWorkspace()
+    ws = wsobj.get(nbytes.value, device)
+    wsobj.last_cfg = cfg
+    if acc is None:
+        acc = new_accumulators(n_partitions, counts, device)
+    sobj = stream if stream is not None else torch.cuda.current_stream(device)
+    st = int(sobj.cuda_stream)
+    N.check(lib.pdp_bound_contributions(ctypes.byref(cfg), _ptr(pid), _ptr(pk), None, _ptr(allowed), _ptr(ws),
+                                        ws.numel(), st), "pdp_bound_contributions")
+    N.check(lib.pdp_reduce_partitions(ctypes.byref(cfg), None, _ptr(ws), ws.numel(),
+                                      ctypes.byref(_acc_struct(acc)), st), "pdp_reduce_partitions")
+    N.check(lib.pdp_reduce_vector_sum(ctypes.byref(cfg), _ptr(pid), _ptr(pk), _ptr(allowed), _ptr(vectors), d,
+                                      _ptr(ws), ws.numel(), _ptr(vector_acc), st), "pdp_reduce_vector_sum")
+    if check_keys == "defer" and workspace is not None:
+        wsobj.defer_error_check(ws, sobj, n_privacy_ids, n_partitions)
+    elif check_keys:
+        flags = ctypes.c_uint32(0)
+        N.check(lib.pdp_bound_error_flags(_ptr(ws), ctypes.byref(flags), st), "pdp_bound_error_flags")
+        _raise_error_flags(flags.value, n_privacy_ids, n_partitions)
+    return acc, vector_acc
+
+
+def vector_sum_metrics(vector_acc, index, *, norm_kind: int, max_norm: float, noise: NoiseParams, seed: int,
+                       n_kept: Optional[int] = None, n_kept_dev=None, partition_offset: int = 0, out=None,
+                       stream=None):
+    """VectorSumCombiner.compute_metrics for the kept partitions
+    (`pdp_vector_sum_metrics`): row i of the result is vector_acc[index[i]]
+    clipped by `norm_kind` (N.NORM_*) to `max_norm`, plus the secure noise
+    `noise` per coordinate (NO_NOISE: clip only).  index: int64 device tensor;
+    n_kept defaults to its length; n_kept_dev (device int64[1]) bounds it on
+    the device.  Returns a float64 device tensor [n_kept, vector_size]."""
+    torch = _torch()
+    lib = N.lib()
+    if not isinstance(vector_acc, torch.Tensor) or vector_acc.dim() != 2:
+        raise TypeError("vector_acc must be a 2-D torch tensor [n_partitions, vector_size] on the GPU")
+    device = vector_acc.device
+    P, d = int(vector_acc.shape[0]), int(vector_acc.shape[1])
+    _check_matrix(vector_acc, "vector_acc", P, d, device)
+    cap = int(index.shape[0])
+    _check_col(index, "index", (torch.int64,), cap, device)
+    n_kept = cap if n_kept is None else int(n_kept)
+    if n_kept < 0 or n_kept > cap:
+        raise ValueError(f"n_kept={n_kept} is outside [0, {cap}]")
+    if n_kept_dev is not None:
+        _check_col(n_kept_dev, "n_kept_dev", (torch.int64,), 1, device)
+    if out is None:
+        out = torch.empty((n_kept, d), dtype=torch.float64, device=device)
+    _check_matrix(out, "out", n_kept, d, device)
+    c_noise = (noise or NO_NOISE).to_c()
+    N.check(lib.pdp_vector_sum_metrics(_ptr(vector_acc), d, int(norm_kind), float(max_norm), ctypes.byref(c_noise),
+                                       _ptr(index), n_kept, _ptr(n_kept_dev), int(partition_offset), _ptr(out),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, _stream(stream)),
+            "pdp_vector_sum_metrics")
+    return out
+
+
 def _raise_error_flags(flags: int, n_privacy_ids, n_partitions):
     if flags & 1:
         raise ValueError("privacy_id / partition_key outside the dense key range "
