@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 15
+#define PDP_ABI_VERSION 16
 
 /* error codes */
 #define PDP_OK 0
@@ -557,6 +557,39 @@ int pdp_dataset_histograms_preaggregated_finish(const double* sum, int64_t n_row
  * value even at count 0.  Device arrays; asynchronous on `stream`. */
 int pdp_dataset_histograms_weight_bins(const uint64_t* keys, const double* weights, int64_t n,
                                        const pdp_histogram_bins* out, void* stream);
+
+/* Private contribution bounds: the device steps of
+ * DPEngine.calculate_private_contribution_bounds (pipeline_dp/dp_engine.py:
+ * 450-502), around pdp_dataset_histograms.
+ *
+ * pdp_filter_rows is DPEngine._drop_partitions (dp_engine.py:417-423) on
+ * dense columns: the rows with allowed[partition[i]] != 0 are written to
+ * out_privacy_id / out_partition (device int64[n_rows] each, they may not
+ * alias the inputs) and their number to *out_count (device int64).  One pass
+ * over the 16 B/row; each 2,048-row tile reserves its output range with one
+ * integer atomic, so rows keep their order within a tile but the tiles' order
+ * in the output is not stable from call to call.  allowed: device
+ * uint8[n_partitions].  A partition outside [0, n_partitions) sets bit 0 of
+ * the error word at the start of `workspace` (pdp_bound_error_flags); the row
+ * is dropped and the mask is not read for it.  Workspace bytes:
+ * pdp_filter_rows_workspace_bytes. */
+int pdp_filter_rows_workspace_bytes(int64_t n_rows, uint64_t* bytes);
+int pdp_filter_rows(const int64_t* privacy_id, const int64_t* partition, const uint8_t* allowed, int64_t n_rows,
+                    int64_t n_partitions, int64_t* out_privacy_id, int64_t* out_partition, int64_t* out_count,
+                    void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* L0ScoringFunction._l0_impact_dropped (private_contribution_bounds.py:
+ * 164-176) for n_candidates bounds at once:
+ *   dropped[c] = sum over bins b of max(min(lower(b), upper_bound) - candidates[c], 0) * l0_count[b]
+ * l0_count: the L0 row of pdp_histogram_bins.int_count (device
+ * int64[PDP_HIST_LOG_BINS], lower(b) as described at pdp_dataset_histograms);
+ * candidates (>= 0; a negative one counts as 0) and dropped: device
+ * int64[n_candidates].  Integer arithmetic, exact while the sum fits: it is
+ * at most (sum of l0_count) * upper_bound, the histogram's counts sum to less
+ * than 2^31 (pdp_dataset_histograms: n_rows < 2^31), so upper_bound <= 2^32
+ * keeps it below 2^63; a larger upper_bound returns PDP_E_UNSUPPORTED. */
+int pdp_l0_impact_dropped(const int64_t* l0_count, int64_t upper_bound, const int64_t* candidates,
+                          int64_t n_candidates, int64_t* dropped, void* stream);
 
 /* Multi-GPU sharding check (ColumnarBackend privacy_id_sharding="verify"):
  * counts the ids whose owner rank is not `rank`, where owner(id) =

@@ -8,9 +8,10 @@ through hand-written HIP kernels (pipelinedp_amd/csrc, C ABI in
 include/pipelinedp_amd.h).  ColumnarBackend also plugs into the reference's
 own pipeline_dp.DPEngine.
 """
-from pipelinedp_amd.aggregate_params import (AddDPNoiseParams, AggregateParams, MechanismType, Metric,
+from pipelinedp_amd.aggregate_params import (AddDPNoiseParams, AggregateParams,
+                                             CalculatePrivateContributionBoundsParams, MechanismType, Metric,
                                              Metrics, NoiseKind, NormKind, PartitionSelectionStrategy,
-                                             SelectPartitionsParams)
+                                             PrivateContributionBounds, SelectPartitionsParams)
 from pipelinedp_amd.budget_accounting import (BudgetAccountant, MechanismSpec, NaiveBudgetAccountant,
                                               PLDBudgetAccountant)
 from pipelinedp_amd.columnar import ColumnTable, DictColumn

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PIPELINEDP_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "lib", "libpipelinedp_amd.so")
 
 # constants (include/pipelinedp_amd.h)
-ABI_VERSION = 15
+ABI_VERSION = 16
 VALUE_NONE, VALUE_F64, VALUE_I64 = 0, 1, 2
 ACC_SUM, ACC_NSUM, ACC_NSUM2, SUM_PER_PARTITION, SUM_INT = 0x1, 0x2, 0x4, 0x8, 0x10
 DEBUG_CORRUPT_RECORDS = 0x40000000  # tests only (pipelinedp_amd.h)
@@ -67,6 +67,9 @@ EXPORTED_SYMBOLS = (
     "pdp_dataset_histograms_preaggregated_finish",
     "pdp_dataset_histograms_preaggregated_weight_offsets",
     "pdp_dataset_histograms_weight_bins",
+    "pdp_filter_rows_workspace_bytes",
+    "pdp_filter_rows",
+    "pdp_l0_impact_dropped",
     "pdp_bound_error_flags",
     "pdp_bound_error_flags_async",
     "pdp_owner_mismatches",
@@ -262,6 +265,9 @@ def signatures():
                                                                        vp, u64, vp]),
         "pdp_dataset_histograms_preaggregated_weight_offsets": (ctypes.c_int, [i64, i64, P(u64), P(u64), P(u64)]),
         "pdp_dataset_histograms_weight_bins": (ctypes.c_int, [vp, vp, i64, P(HistogramBins), vp]),
+        "pdp_filter_rows_workspace_bytes": (ctypes.c_int, [i64, P(u64)]),
+        "pdp_filter_rows": (ctypes.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, vp, u64, vp]),
+        "pdp_l0_impact_dropped": (ctypes.c_int, [vp, i64, vp, i64, vp, vp]),
         "pdp_bound_error_flags": (ctypes.c_int, [vp, P(ctypes.c_uint32), vp]),
         "pdp_bound_error_flags_async": (ctypes.c_int, [vp, vp, vp]),
         "pdp_owner_mismatches": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),

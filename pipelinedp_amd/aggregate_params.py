@@ -3,7 +3,8 @@
 Same names, fields, defaults and validation rules as
 pipeline_dp/aggregate_params.py (reference): Metric/Metrics (:28-72),
 NoiseKind (:75-83), PartitionSelectionStrategy (:86-89), MechanismType
-(:92-117), AggregateParams (:189-395), SelectPartitionsParams (:398-425),
+(:92-117), CalculatePrivateContributionBoundsParams / PrivateContributionBounds
+(:136-186), AggregateParams (:189-395), SelectPartitionsParams (:398-425),
 AddDPNoiseParams (:645-675), parameters_to_readable_string (:707-738).
 """
 import dataclasses
@@ -129,6 +130,38 @@ def _require_positive_int(value: Any, field_name: str):
 
 def _not_finite(num: Any) -> bool:
     return math.isnan(num) or math.isinf(num)
+
+
+@dataclasses.dataclass
+class CalculatePrivateContributionBoundsParams:
+    """Parameters of DPEngine.calculate_private_contribution_bounds (reference
+    aggregate_params.py:136-173).  The aggregation the bound is meant for is
+    COUNT or PRIVACY_ID_COUNT: aggregation_noise_kind / _eps / _delta are that
+    aggregation's, calculation_eps is what choosing the bound spends, and
+    max_partitions_contributed_upper_bound the largest bound considered."""
+    aggregation_noise_kind: NoiseKind
+    aggregation_eps: float
+    aggregation_delta: float
+    calculation_eps: float
+    max_partitions_contributed_upper_bound: int
+
+    def __post_init__(self):
+        validate_epsilon_delta(self.aggregation_eps, self.aggregation_delta,
+                               "CalculatePrivateContributionBoundsParams")
+        if self.aggregation_noise_kind is None:
+            raise ValueError("aggregation_noise_kind must be set.")
+        if self.aggregation_noise_kind == NoiseKind.GAUSSIAN and self.aggregation_delta == 0:
+            raise ValueError("The Gaussian noise requires that the aggregation_delta is greater than 0.")
+        validate_epsilon_delta(self.calculation_eps, 0, "CalculatePrivateContributionBoundsParams")
+        _require_positive_int(self.max_partitions_contributed_upper_bound,
+                              "max_partitions_contributed_upper_bound")
+
+
+@dataclasses.dataclass
+class PrivateContributionBounds:
+    """Contribution bounds chosen differentially privately, for COUNT and
+    PRIVACY_ID_COUNT aggregations (reference aggregate_params.py:176-186)."""
+    max_partitions_contributed: int
 
 
 @dataclasses.dataclass

@@ -20,6 +20,7 @@ python-dp (PyDP ~=1.1.5rc4, Google differential-privacy C++):
 These are scalars computed once per aggregation on the host; the per-partition
 work (noise draws, keep decisions) runs in the HIP kernels.
 """
+import abc
 import dataclasses
 import functools
 import math
@@ -565,6 +566,79 @@ def noise_scale(noise_kind: agg.NoiseKind, eps: float, delta: float, l0: float, 
     if noise_kind == agg.NoiseKind.GAUSSIAN:
         return compute_sigma(eps, delta, compute_l2_sensitivity(l0, linf))
     raise ValueError("Noise kind must be either Laplace or Gaussian.")
+
+
+@functools.lru_cache(maxsize=8192)
+def _cached_sigma(eps: float, delta: float, l0: int, linf: float) -> float:
+    """compute_sigma per (eps, delta, l0, linf): the private-bounds score asks
+    for one sigma per candidate bound (a few thousand bisections), again on
+    every call with the same budget.  Bounded by entries (least recently used
+    out first)."""
+    return compute_sigma(eps, delta, compute_l2_sensitivity(l0, linf))
+
+
+def _compute_noise_std(linf_sensitivity: float, dp_params: ScalarNoiseParams) -> float:
+    """dp_computations.py:368-381."""
+    if dp_params.noise_kind == agg.NoiseKind.LAPLACE:
+        l1 = compute_l1_sensitivity(dp_params.l0_sensitivity(), linf_sensitivity)
+        return laplace_diversity(dp_params.eps, l1) * np.sqrt(2)
+    if dp_params.noise_kind == agg.NoiseKind.GAUSSIAN:
+        return _cached_sigma(dp_params.eps, dp_params.delta, dp_params.l0_sensitivity(), linf_sensitivity)
+    raise ValueError("Only Laplace and Gaussian noise is supported.")
+
+
+def compute_dp_count_noise_std(dp_params: ScalarNoiseParams) -> float:
+    """Noise standard deviation of a DP count (dp_computations.py:384-387):
+    Laplace l0 * linf / eps * sqrt(2), Gaussian compute_sigma's."""
+    return _compute_noise_std(dp_params.max_contributions_per_partition, dp_params)
+
+
+# ---------------------------------------------------------- exponential mechanism --
+class ExponentialMechanism:
+    """Chooses one of a list of parameters differentially privately
+    (dp_computations.py:661-715): P(k) proportional to
+    exp(score(k) * eps / global_sensitivity), the denominator doubled for a
+    non-monotonic score.  All in memory.
+
+    One deviation from the reference: the exponents are shifted by their
+    maximum before np.exp.  The reference's np.exp(scores * eps / sensitivity)
+    underflows to all zeros (0 / 0 = NaN probabilities) once every exponent is
+    below about -745; the shifted form is the same softmax, equal to the
+    reference's wherever that one is finite."""
+
+    class ScoringFunction(abc.ABC):
+        """The score of a parameter: the higher, the likelier it is chosen."""
+
+        @abc.abstractmethod
+        def score(self, k) -> float:
+            """Score of parameter k."""
+
+        @property
+        @abc.abstractmethod
+        def global_sensitivity(self) -> float:
+            """Global sensitivity of the score."""
+
+        @property
+        @abc.abstractmethod
+        def is_monotonic(self) -> bool:
+            """Whether, for neighbouring datasets D and D', score(D, k) >=
+            score(D', k) for every k or <= for every k."""
+
+    def __init__(self, scoring_function: "ExponentialMechanism.ScoringFunction") -> None:
+        self._scoring_function = scoring_function
+
+    def apply(self, eps: float, inputs_to_score_col: List[Any]) -> Any:
+        probs = self._calculate_probabilities(eps, inputs_to_score_col)
+        return np.random.default_rng().choice(inputs_to_score_col, p=probs)
+
+    def _calculate_probabilities(self, eps: float, inputs_to_score_col: List[Any]):
+        scores = np.array(list(map(self._scoring_function.score, inputs_to_score_col)))
+        denominator = self._scoring_function.global_sensitivity
+        if not self._scoring_function.is_monotonic:
+            denominator *= 2
+        exponents = scores * eps / denominator
+        weights = np.exp(exponents - exponents.max())
+        return weights / weights.sum()
 
 
 # ------------------------------------------------------------------ vector sums --

@@ -970,6 +970,61 @@ def dataset_histograms(pid, pk, value, *, n_privacy_ids: int, n_partitions: int,
     return out
 
 
+def filter_rows(pid, pk, allowed, *, n_partitions: int, stream=None, check_keys: bool = True):
+    """DPEngine._drop_partitions on device columns of dense codes
+    (`pdp_filter_rows`): the rows whose partition has allowed[pk] != 0,
+    compacted in one pass.  Returns (pid_kept, pk_kept): prefixes of two new
+    int64 columns (reading their length synchronises the stream).  The order
+    of the kept rows is not stable across 2,048-row tiles.  A partition code
+    outside [0, n_partitions) raises the key-range ValueError (check_keys)."""
+    torch = _torch()
+    lib = N.lib()
+    if not pk.is_cuda:
+        raise ValueError("columns must be device tensors")
+    device = pk.device
+    n = int(pk.numel())
+    P = int(n_partitions)
+    _check_col(pid, "privacy_id", (torch.int64,), n, device)
+    _check_col(pk, "partition", (torch.int64,), n, device)
+    _check_col(allowed, "allowed", (torch.uint8,), P, device)
+    nbytes = ctypes.c_uint64()
+    N.check(lib.pdp_filter_rows_workspace_bytes(n, ctypes.byref(nbytes)), "pdp_filter_rows_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    out_pid = torch.empty(n, dtype=torch.int64, device=device)
+    out_pk = torch.empty(n, dtype=torch.int64, device=device)
+    count = torch.empty(1, dtype=torch.int64, device=device)
+    sptr = _stream(stream)
+    N.check(lib.pdp_filter_rows(_ptr(pid), _ptr(pk), _ptr(allowed), n, P, _ptr(out_pid), _ptr(out_pk), _ptr(count),
+                                _ptr(ws), int(ws.numel()), sptr), "pdp_filter_rows")
+    if check_keys:
+        flags = ctypes.c_uint32()
+        N.check(lib.pdp_bound_error_flags(_ptr(ws), ctypes.byref(flags), sptr), "pdp_bound_error_flags")
+        if flags.value & 1:
+            raise ValueError(f"partition_key outside the dense key range [0, {P})")
+    kept = int(count.item())
+    return out_pid[:kept], out_pk[:kept]
+
+
+def l0_impact_dropped(l0_count, upper_bound: int, candidates, stream=None):
+    """L0ScoringFunction._l0_impact_dropped for every candidate bound
+    (`pdp_l0_impact_dropped`): l0_count is the L0 row of
+    dataset_histograms(...)["int_count"], candidates a device int64 column;
+    returns dropped[c] = sum_b max(min(lower(b), upper_bound) - candidates[c], 0)
+    * l0_count[b] as a device int64 column (exact)."""
+    torch = _torch()
+    lib = N.lib()
+    if not l0_count.is_cuda:
+        raise ValueError("l0_count must be a device tensor")
+    device = l0_count.device
+    _check_col(l0_count, "l0_count", (torch.int64,), N.HIST_LOG_BINS, device)
+    m = int(candidates.numel())
+    _check_col(candidates, "candidates", (torch.int64,), m, device)
+    out = torch.empty(m, dtype=torch.int64, device=device)
+    N.check(lib.pdp_l0_impact_dropped(_ptr(l0_count), int(upper_bound), _ptr(candidates), m, _ptr(out),
+                                      _stream(stream)), "pdp_l0_impact_dropped")
+    return out
+
+
 def _histogram_outputs(device):
     torch = _torch()
     i64 = dict(dtype=torch.int64, device=device)
