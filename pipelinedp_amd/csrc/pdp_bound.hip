@@ -28,81 +28,26 @@
 //                      B1 bottom-l0 pair sketch per pid, B2 per-pair row count
 //                      + bottom-linf row sketch, B3 gather the sampled values
 //                      and merge each kept pair into the partition accumulators
+//    k_range_*, k_split_*, k_fine_*   PDP_MERGE_RANGES: the pair records summed
+//                      per partition (pdp_bound_merge.hip, launch_merge)
 //  GLOBAL (fallback for large l0 * linf)
 //    k_pair_sketch / k_pair_rows / k_reduce_pairs: the same sketches in HBM,
 //    updated with device-scope atomics.
+//
+// Where the code lives: every kernel above is in this file but the k_scan_*
+// (pdp_scan.hip, scan_u32) and the range merge (pdp_bound_merge.hip); this
+// file also holds validate, the plan (make_plan, layout, make_kp) and the C
+// entry points.  pdp_bound_plan.h: the shared constants, Plan, Ws, KP,
+// PairRecords; pdp_bound_keys.h: device helpers of more than one file.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
 
-#include "pdp_internal.h"
+#include "pdp_bound_keys.h"
 
 namespace pdp {
 namespace {
-
-constexpr int kPartThreads = 512;
-// rows per thread and LDS stage of the level-1 scatter / level-2 window
-constexpr int kL1Threads = 1024;
-constexpr int kL1Items = 8;
-constexpr int kL1Rows = kL1Threads * kL1Items;  // rows per level-1 LDS stage
-constexpr int kL2Items = 16;
-// level 2: two 8-wave workgroups per CU need <= 128 VGPRs (MI355X_MICROARCH.md
-// register table): the kernel takes 121-123 with 16 records per thread;
-// loading a stage ahead (157 VGPRs, one workgroup per CU) cost 1 ms at C3
-constexpr int kL2Threads = 512;
-constexpr int kL2Rows = kL2Threads * kL2Items;  // records per level-2 LDS stage
-// tiles per level-2 workgroup (k_scatter_l2, k_gscan_cursors)
-constexpr int kL2GroupTiles = 16;
-constexpr int kScanWaves = 16;
-constexpr int kScanTiles = 16;  // tiles per wave in the level-2 cursor scans; multiple of kL2GroupTiles
-constexpr int kScanChunkTiles = kScanWaves * kScanTiles;
-static_assert(kScanTiles % kL2GroupTiles == 0, "group starts must fall inside a wave's tiles");
-constexpr int kTileRowBits = 16;
-constexpr int64_t kTileRows = (int64_t)1 << kTileRowBits;
-constexpr int kStagesPerTile = (int)(kTileRows / kL1Rows);  // level-1 blocks per tile
-constexpr int kL2Runs = kL2GroupTiles * kStagesPerTile;  // level-1 runs per level-2 workgroup
-constexpr int kUnroll = 8;
-constexpr int kBucketThreads = 1024;
-constexpr int64_t kLdsBudget = 124 * 1024;  // per-pid state; + range scratch + wave queues <= 160 KiB
-// 512-thread bucket workgroups: per-pid state <= 56 KiB, so that with the
-// range scratch (<= 4 KiB at 512 ranges), 8 wave queues (12 KiB) and the pid
-// hashes two workgroups fit one CU's 160 KiB
-constexpr int64_t kLdsBudget2 = 56 * 1024;
-constexpr int kMinRandomBits = 24;
-constexpr int64_t kMaxBuckets = 36 * 1024;  // u32 histogram in 144 KiB of LDS
-constexpr int kMaxSupers = 128;   // destinations of a level-1 scatter
-constexpr int64_t kSingleLevelMax = 64;      // buckets partitioned by one level
-constexpr int kRangeBits = 11;                // partitions per merge range = 2048
-constexpr int kRangeParts = 1 << kRangeBits;
-constexpr int kMaxRanges = kBucketThreads;    // per-bucket range histogram <= one block scan
-// More partitions than kMaxRanges ranges of 2^kRangeBits: the bucket kernel
-// groups kept pairs by coarse ranges of 2^range_bits partitions (<= kCoarseRanges
-// of them), k_split_* re-sort each coarse range's records into its
-// 2^kRangeBits-partition ranges, k_fine_reduce sums them (two-level merge)
-constexpr int kCoarseRanges = 256;
-#ifndef PDP_RANGE_THREADS
-#define PDP_RANGE_THREADS 1024
-#endif
-constexpr int kRangeThreads = PDP_RANGE_THREADS;  // k_range_plan workgroups
-// range-reduce work item: the records of one partition range from a run of
-// consecutive buckets, cut at bucket boundaries every kRangeChunk records
-// (k_range_plan), so a Zipf-hot range spreads over many workgroups and a cold
-// one is a single item
-constexpr int64_t kRangeChunk = 8192;
-constexpr unsigned kRangeDirect = 256;        // records below which a workgroup adds them directly
-// k_range_reduce / k_fine_reduce workgroups: 512 threads (two per CU by their
-// 68 KB of LDS: 16 waves, not 8): C3 k_range_reduce 0.275 -> 0.195 ms, C4
-// k_fine_reduce 0.574 -> 0.540 (1,024: 0.212 / 0.537; profiles/r05/ab/ab12_merge_threads.txt)
-constexpr int kReduceThreads = 512;
-#ifndef PDP_SPLIT_THREADS
-#define PDP_SPLIT_THREADS 512
-#endif
-constexpr int kSplitThreads = PDP_SPLIT_THREADS;  // k_split_count / k_split_scatter workgroups
-constexpr size_t kRangeLds = kRangeParts * (3 * 8 + 2 * 4) + kReduceThreads * (8 + 4) + (kReduceThreads / 64 + 1) * 4;
-constexpr int kQueueCap = 128;                // per-wave candidate queue (bucket kernel)
-constexpr int kScanItems = 16;
-constexpr int kScanChunk = kBlock * kScanItems;
 
 constexpr int64_t kL1LocalLds = 150 * 1024;  // tile-local level 1: LDS cap (one 1,024-thread workgroup per CU)
 size_t l1_stage_bytes(int key_format);       // LDS of one level-1 stage (after StageLds)
@@ -128,14 +73,8 @@ inline bool l1_hist_u16(int key_format, int64_t n_buckets) {
 // the list in front of the exact bitmap), a scatter into bucket order and a
 // second bucket-kernel launch whose pair records follow the main ones.
 // Kept pairs and rows are exactly those of the unsieved path.
-#ifndef PDP_SIEVE_BUFS
-#define PDP_SIEVE_BUFS 2
-#endif
-#ifndef PDP_SIEVE_EARLY
-#define PDP_SIEVE_EARLY 0
-#endif
 constexpr int kSieveChunkItems = 4;                            // rows per thread and chunk
-constexpr int kSieveBufs = PDP_SIEVE_BUFS;  // full tiles: chunks of loads in flight (register buffers)
+constexpr int kSieveBufs = 2;  // full tiles: chunks of loads in flight (register buffers)
 constexpr int kSieveItems = 12;  // stage slots per thread (records each thread handles at a flush)
 // Two workgroup shapes (Plan.sieve_threads):
 //  1,024 threads, a 12,288-candidate stage, 8 flush slots per tile: one
@@ -165,13 +104,6 @@ constexpr int64_t kSieveLds2 = 80 * 1024 - 256;  // two 512-thread workgroups pe
 // lists k_band_scan streams (C3 0.277 -> 0.255 ms); measured neutral or worse
 // and not used: k_scatter_l1_local's key loads (C4 +0.03 ms), level 2's run
 // loads and the bucket kernel's record stream (profiles/r05/ab/ab5_nt_loads.txt)
-#ifndef PDP_L1_NT
-#define PDP_L1_NT 1
-#endif
-#ifndef PDP_NT_BS
-#define PDP_NT_BS 1
-#endif
-
 constexpr int64_t kSieveTileStride = kTileRows;
 constexpr int64_t kBandTileStride = kTileRows;
 constexpr int kSieveMaxT16 = 1 << 15;                          // t <= 1/2
@@ -204,37 +136,6 @@ inline int64_t sieve_lds(int key_format, int threads, int64_t n_buckets, bool u1
          (band ? sieve_band_lds(threads) : 0);
 }
 
-struct Plan {
-  int algorithm;   // PDP_ALGO_*
-  int pk_bits;
-  int bucket_bits;
-  int super_bits;
-  int rand_shift;
-  int64_t n_buckets;
-  int64_t n_supers;
-  int64_t n_tiles;
-  int64_t lds_bytes;
-  int merge;            // PDP_MERGE_* (bucketed)
-  int n_ranges;         // PDP_MERGE_RANGES: ceil(P / 2^range_bits)
-  int range_bits;       // partitions per merge range of the bucket kernel (kRangeBits, or coarse)
-  int two_level;        // range_bits > kRangeBits: coarse ranges, then k_split_* / k_fine_*
-  int64_t n_fine;       // two-level: ceil(P / 2^kRangeBits)
-  int64_t fine_items;   // two-level: upper bound on the k_fine_reduce work items
-  int64_t range_group;  // records per range-reduce work item (kRangeChunk)
-  int64_t n_groups;     // upper bound on the range-reduce work items (+ one sentinel per range)
-  int key_format;       // PDP_KEYS_WIDE / PDP_KEYS_COMPACT (bucketed)
-  int l1_local;         // tile-local level 1 (k_scatter_l1_local / k_scatter_l2_local), no histogram pass
-  int64_t n_stages;     // level-1 stages of kL1Rows rows
-  int sieve;            // threshold sieve: t = sieve / 2^16 (0 = off); k_sieve_l1 instead of k_scatter_l1_local
-  int band;             // side band: t2 = band / 2^16 (0 = off; else 2 * sieve, <= 1/2)
-  int64_t n_slots1;     // level-1 blocks (stages, or sieve flush slots: n_tiles << slot_bits)
-  int64_t buckets_out;  // buckets of pair records: n_buckets, x2 with the sieve (fix-up after), x3 with the band
-  int l2_mult;          // tile groups per level-2 workgroup (1 without the sieve)
-  int sieve_threads;    // k_sieve_l1 workgroup: 1,024 or 512 threads (SieveShape)
-  int bucket_threads;   // k_bucket_bound workgroup: 1,024 or 512 threads (half-size buckets)
-  int slot_bits;        // level-1 blocks per tile = 2^slot_bits (kStagesPerTile, or SieveShape::kSlots)
-  int hist_u16;         // tile-local level 1 counts buckets in u16 halves (counts_tm / counts_tm2)
-};
 
 int64_t per_pid_lds(const pdp_bound_config* c) {
   const int64_t l0 = c->l0;
@@ -445,41 +346,6 @@ Plan make_plan(const pdp_bound_config* c) {
   return p;
 }
 
-struct Ws {
-  // common
-  uint64_t err;
-  // global path
-  uint64_t sketch, cnt, rows, fsum, nsum, nsum2;
-  // bucketed path
-  uint64_t counts_tm, counts, chunk_sums, super_base, super_tm, super_off, keys1, rows1, keys2, rows2;
-  uint64_t csum, gcur;  // level-2 cursor scans: per tile chunk, per tile group (x n_buckets)
-  uint64_t cand_key, cand_idx;  // bucket kernel: B1's candidate list (record-local key, row)
-  uint64_t soff;                // tile-local level 1: per stage, super-bucket run starts (u16)
-  uint64_t counts_tm2;          // tile-local level 1, u16 counts: second half-tile bucket counts
-  // threshold sieve: flush-block starts (u32 per slot), unresolved privacy
-  // ids (bitmap + list), {unresolved count, fix-up rows}, fix-up rows per
-  // bucket (-> starts) and their write cursors; the fix-up row list itself
-  // reuses keys1 (dead after level 2), its bucket-ordered records keys2/rows2
-  uint64_t sbase, unres_bits, unres_list, sctl, fix_cnt, fix_cur;
-  // the fix-up's (id << 32 | row) list: the level-1 region (keys1, and rows1
-  // right after it for COMPACT records), dead after level 2; fix_cap entries
-  // (>= n_rows: every list holds distinct rows)
-  uint64_t fix_rec, fix_cap;
-  // side band: per-tile (pid << 32 | row) lists and their lengths; the ids
-  // still unresolved after the band fix-up (bitmap, list, {count, rows}) and
-  // their rescan's per-bucket counts / cursors
-  uint64_t band, band_cnt, unres2_bits, unres2_list, sctl2, fix_cnt2, fix_cur2;
-  uint64_t fix_blist;  // fix-up bucket launches: {count, buckets holding fix-up rows...}
-  uint64_t tile_over;  // tile-local level 1: per tile, the bucket holding all 65,536 of its rows (else ~0)
-  // bucketed PDP_MERGE_RANGES: pair records per bucket block, grouped by range
-  uint64_t runs, rec_key, rec_f0, rec_f1, rec_f2;
-  uint64_t rr_items, rr_count;  // range-reduce work items (uint4) and their count
-  // two-level merge: fine-range totals / starts (+ scan scratch), write cursors,
-  // the records re-sorted by fine range, fine work items and their count
-  uint64_t fine_total, fine_chunks, fine_cur, stg_key, stg_f0, stg_f1, stg_f2, fine_items, fine_count;
-  uint64_t item_hist;  // two-level: per coarse work item, its records per fine range (k_split_count)
-  uint64_t total;
-};
 
 // row stride of the per-tile bucket counts in buckets (KP.cstride): whole
 // 16-byte rows of u16 pairs (tile-local level 1) or u32 counts, so
@@ -638,29 +504,6 @@ int validate(const pdp_bound_config* c) {
 }
 
 
-struct KP {  // kernel parameters
-  int64_t n, U, P;
-  int l0, linf;
-  int pk_bits, bucket_bits, super_bits, rand_shift;
-  int64_t n_buckets, n_supers, n_tiles;
-  int n_ranges;
-  int range_bits;
-  int64_t n_fine_ranges;  // two-level merge: ceil(P / 2^kRangeBits)
-  int keys_vec;  // privacy_id / partition_key columns are 16-byte aligned
-  uint64_t pk_mask, seed, row_seed;
-  int64_t row_offset;
-  int64_t cstride;  // row stride of counts_tm / counts_tm2 in buckets: n_buckets rounded up to 8
-  ClipParams clip;
-  int64_t n_slots1;     // level-1 blocks read by level 2 (Plan.n_slots1)
-  int l2_group_mult;    // tile groups per level-2 workgroup
-  uint32_t sieve_t32;   // threshold sieve: candidate rows have pair_hash < sieve_t32 (0 = off)
-  int sieve_mark;       // bucket kernel: mark privacy ids with < l0 candidate pairs unresolved
-  uint32_t band_t32;    // side band: level 1 lists rows with sieve_t32 <= pair_hash < band_t32 (0 = off)
-  int sieve_emit;       // bucket kernel (main launch, band on): unresolved ids' candidate rows -> fix_rec
-  int slot_bits;        // level-1 blocks per tile = 2^slot_bits (Plan.slot_bits)
-  int64_t fix_cap;      // sieve: entries the fix-up row list (fix_rec, Ws.fix_rec) holds
-  int row_shift;        // PACKED64 level-2 records: the row's first bit (pk_bits + bucket_bits)
-};
 
 KP make_kp(const pdp_bound_config* c, const Plan& p) {
   KP k;
@@ -1075,6 +918,33 @@ inline int rec_of(int key_format) {
                                                 ? kRecWide : kRecCompact);
 }
 
+// ------------------------------------------------------ format visitors --
+// f(std::integral_constant<int, X>{}) for a run-time record kind, key format
+// or (value kind, keep every row): the one place each ladder is written
+template <typename F>
+int with_rec(int kind, F&& f) {
+  if (kind == kRecCompact) return f(std::integral_constant<int, kRecCompact>{});
+  if (kind == kRecWide) return f(std::integral_constant<int, kRecWide>{});
+  return f(std::integral_constant<int, kRecP64>{});
+}
+template <typename F>
+int with_key_format(int fmt, F&& f) {
+  if (fmt == PDP_KEYS_COMPACT) return f(std::integral_constant<int, PDP_KEYS_COMPACT>{});
+  if (fmt == PDP_KEYS_PACKED) return f(std::integral_constant<int, PDP_KEYS_PACKED>{});
+  if (fmt == PDP_KEYS_PACKED_WIDE) return f(std::integral_constant<int, PDP_KEYS_PACKED_WIDE>{});
+  if (fmt == PDP_KEYS_PACKED64) return f(std::integral_constant<int, PDP_KEYS_PACKED64>{});
+  return f(std::integral_constant<int, PDP_KEYS_WIDE>{});
+}
+template <typename F>
+int with_value(int value_kind, bool keep_all, F&& f) {
+  auto kind = [&](auto ka) {
+    if (value_kind == PDP_VALUE_NONE) return f(std::integral_constant<int, PDP_VALUE_NONE>{}, ka);
+    if (value_kind == PDP_VALUE_F64) return f(std::integral_constant<int, PDP_VALUE_F64>{}, ka);
+    return f(std::integral_constant<int, PDP_VALUE_I64>{}, ka);
+  };
+  return keep_all ? kind(std::true_type{}) : kind(std::false_type{});
+}
+
 // MAXD destinations per stage; the small form (<= 256 destinations, u8 tags)
 // fits four workgroups per CU with compact keys instead of three.  ROWS:
 // the stage carries a u32 row array beside the keys.
@@ -1424,33 +1294,6 @@ __global__ void __launch_bounds__(kL2Threads)  k_scatter_l2(KP kp, const unsigne
     for (int t = threadIdx.x; t < nsub; t += blockDim.x) s.gcur[t] += s.hist[t];
     __syncthreads();
   }
-}
-
-// exclusive block-wide scan of one u32 per thread; wsum = LDS[blockDim/64]
-__device__ __forceinline__ unsigned block_excl_scan(unsigned x, unsigned* wsum, unsigned* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  unsigned inc = x;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned y = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += y;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  if (w == 0) {
-    const unsigned v = lane < nw ? wsum[lane] : 0;
-    unsigned vi = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned y = __shfl_up(vi, off, 64);
-      if (lane >= off) vi += y;
-    }
-    if (lane < nw) wsum[lane] = vi - v;
-    if (lane == nw - 1) wsum[nw] = vi;
-  }
-  __syncthreads();
-  *total = wsum[nw];
-  return wsum[w] + inc - x;
 }
 
 // super_off[t][B] = rows of super-bucket B in tiles < t (exclusive scan over
@@ -1841,8 +1684,8 @@ __global__ void __launch_bounds__(TH, TH == kL1Threads ? 1 : 4) k_sieve_l1(KP kp
       for (int q = 0; q < Q; q += 2) {
         const int64_t i = c0 + 2 * ((int64_t)threadIdx.x + (int64_t)(q / 2) * TH);
         if constexpr (FULL) {
-          const longlong2 a = ld_maybe_nt<PDP_L1_NT>(reinterpret_cast<const longlong2*>(pid + i));
-          const longlong2 c = ld_maybe_nt<PDP_L1_NT>(reinterpret_cast<const longlong2*>(pk + i));
+          const longlong2 a = ld_nt(reinterpret_cast<const longlong2*>(pid + i));
+          const longlong2 c = ld_nt(reinterpret_cast<const longlong2*>(pk + i));
           u[q] = a.x;
           u[q + 1] = a.y;
           k[q] = c.x;
@@ -1883,7 +1726,7 @@ __global__ void __launch_bounds__(TH, TH == kL1Threads ? 1 : 4) k_sieve_l1(KP kp
       // two buffers: the next loads go out now; three or more: after the
       // append / flush below, so that a flush runs with the other buffers'
       // loads in flight and this one's registers free (the register peak)
-      constexpr bool kEarly = !FULL || kSieveBufs < 3 || PDP_SIEVE_EARLY;
+      constexpr bool kEarly = !FULL || kSieveBufs < 3;
       auto prefetch = [&]() {
         if constexpr (FULL) {  // past the tile: the next tile's chunk, else clamped (no branch)
           const int64_t ahead = c0 + kSieveBufs * kSieveChunk;
@@ -2384,14 +2227,6 @@ __device__ __forceinline__ int64_t xcd_major(int64_t id, int64_t G) {
   return x * q + (x < rem ? x : rem) + j;
 }
 
-struct PairRecords {  // PDP_MERGE_RANGES output of the bucket kernel
-  unsigned* runs;                // [n_ranges + 1][run_stride] run starts within the bucket block (range-major)
-  int64_t run_stride;            // buckets_out: one column per output bucket
-  unsigned long long* key;       // (partition << 32) | count
-  double* f0;                    // sum (int64 bits with PDP_SUM_INT)
-  double* f1;                    // normalized sum
-  double* f2;                    // normalized sum of squares
-};
 
 // PDP_PHASE_CLOCK (profiling builds only, tools/build_variants.sh): thread 0
 // of a few buckets prints the wall-clock time (10 ns ticks) of each phase of
@@ -2959,7 +2794,7 @@ __global__ void __launch_bounds__(kRescanThreads) k_band_scan(KP kp, const unsig
 #pragma unroll
         for (int v = 0; v < KU; ++v) {
           const int64_t j = j0 + v * 64 + lane;
-          e[v] = j < cnt ? ld_maybe_nt<PDP_NT_BS>(bt + j) : ~0ULL;
+          e[v] = j < cnt ? ld_nt(bt + j) : ~0ULL;
         }
 #pragma unroll
         for (int v = 0; v < KU; ++v) {
@@ -3082,719 +2917,33 @@ __global__ void __launch_bounds__(kBlock) k_fix_buckets(KP kp, const unsigned* _
   }
 }
 
-// PDP_MERGE_RANGES work items.  Range r's records, taken bucket-major, are cut
-// into items at bucket boundaries: a new item starts after the bucket that
-// holds record position k * kRangeChunk (k >= 1), so every item holds about
-// kRangeChunk records or one bucket's run, a Zipf-hot range spreads over many
-// workgroups and a cold range is one item.  Range r appends its K_r =
-// ceil(total_r / C) items plus a sentinel at a base taken with one atomicAdd
-// (ranges land in any order); entry k + 1 holds item k's end.  Entry:
-// {r | sentinel << 31, first bucket, first record position within the range}.
-// last_ids (the band's second fix-up): its id count; 0 leaves the last
-// `last_buckets` buckets (that launch's record segment) empty, so they are
-// not read
-__global__ void __launch_bounds__(kRangeThreads) k_range_plan(KP kp, const unsigned* __restrict__ runs,
-                                                              uint4* __restrict__ items,
-                                                              unsigned* __restrict__ n_items,
-                                                              const unsigned* __restrict__ last_ids,
-                                                              int64_t last_buckets) {
-  __shared__ unsigned wsum[kRangeThreads / 64 + 1];
-  __shared__ unsigned s_base;
-  const int r = blockIdx.x;
-  const int64_t stride = kp.n_buckets;  // range-major: row r is contiguous over buckets
-  const int64_t n_buckets = last_ids != nullptr && *last_ids == 0u ? kp.n_buckets - last_buckets : kp.n_buckets;
-  auto len_of = [&](int64_t b) -> unsigned {
-    if (b >= n_buckets) return 0u;
-    const unsigned* run = runs + r * stride + b;
-    return run[stride] - run[0];
-  };
-  unsigned total = 0;
-  for (int64_t c = 0; c < n_buckets; c += blockDim.x) {
-    unsigned t;
-    block_excl_scan(len_of(c + threadIdx.x), wsum, &t);
-    total += t;
-    __syncthreads();
-  }
-  if (total == 0) return;  // block-uniform: no items
-  const unsigned C = (unsigned)kRangeChunk;
-  const unsigned K = (total + C - 1) / C;
-  if (threadIdx.x == 0) s_base = atomicAdd(n_items, K + 1);
-  __syncthreads();
-  const unsigned base = s_base;
-  if (threadIdx.x == 0) items[base] = make_uint4((unsigned)r, 0u, 0u, 0u);
-  if (threadIdx.x == 0 && total % C != 0)
-    items[base + K] = make_uint4((unsigned)r | 0x80000000u, (unsigned)n_buckets, total, 0u);
-  unsigned carry = 0;
-  for (int64_t c = 0; c < n_buckets; c += blockDim.x) {
-    const int64_t b = c + threadIdx.x;
-    const unsigned len = len_of(b);
-    unsigned t;
-    const unsigned ex = carry + block_excl_scan(len, wsum, &t);
-    if (len > 0) {
-      // items k >= 1 with k * C in (ex, ex + len] start after this bucket
-      const unsigned e = ex + len;
-      for (unsigned k = ex / C + 1; k * C <= e; ++k)
-        items[base + k] = make_uint4((unsigned)r | (k == K ? 0x80000000u : 0u), (unsigned)(b + 1), e, 0u);
-    }
-    carry += t;
-    __syncthreads();
-  }
-}
-
-// PDP_MERGE_RANGES: one workgroup per work item (k_range_plan) sums its
-// records of partitions [r*2^11, (r+1)*2^11) in LDS, then adds the partial
-// sums with coalesced device atomics (an item of few records adds them
-// directly).
-// workgroup -> work item: i * p mod n for the prime p = 2^31 - 1 > n (a
-// bijection on [0, n)), so the many items of a Zipf-hot range, which k_range_plan
-// lists together, run spread over the launch instead of side by side (their
-// device atomics go to the same partitions)
-__device__ __forceinline__ unsigned item_order(unsigned i, unsigned n) {
-  return (unsigned)(((uint64_t)i * 2147483647ull) % (uint64_t)n);
-}
-
-__global__ void __launch_bounds__(kReduceThreads) k_range_reduce(KP kp, PairRecords rec, const uint4* __restrict__ items,
-                                                               const unsigned* __restrict__ n_items,
-                                                               pdp_partition_accumulators acc, unsigned* err) {
-  extern __shared__ unsigned long long smem[];
-  double* s0 = (double*)smem;               // [kRangeParts] sum
-  double* s1 = s0 + kRangeParts;            // normalized sum
-  double* s2 = s1 + kRangeParts;            // normalized sum of squares
-  unsigned long long* start = (unsigned long long*)(s2 + kRangeParts);  // [kReduceThreads]
-  unsigned* pc = (unsigned*)(start + kReduceThreads);  // [kRangeParts] kept pairs
-  unsigned* cn = pc + kRangeParts;                    // [kRangeParts] row count
-  unsigned* pre = cn + kRangeParts;                   // [kReduceThreads] run prefix
-  unsigned* wsum = pre + kReduceThreads;              // block-scan scratch
-  const unsigned n_it = *n_items;
-  if (blockIdx.x >= n_it) return;  // grid is an upper bound on the item count
-  const unsigned iw = item_order(blockIdx.x, n_it);
-  const uint4 it = items[iw];
-  if (it.x >> 31) return;  // sentinel
-  const uint4 nx = items[iw + 1];
-  const int r = (int)it.x;
-  const int64_t b_lo = it.y, b_hi = nx.y;
-  const unsigned item_total = nx.z - it.z;
-  if (item_total == 0) return;
-  const int flags = kp.clip.flags;
-  const bool f0 = flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION), f1 = flags & PDP_ACC_NSUM,
-             f2 = flags & PDP_ACC_NSUM2, sum_int = flags & PDP_SUM_INT;
-  const int64_t p0 = (int64_t)r << kRangeBits;
-  const int64_t n_slots = (int64_t)kp.l0 << kp.bucket_bits;
-  const bool direct = item_total < kRangeDirect;  // few records: straight into the accumulators
-  if (!direct) {
-    for (int t = threadIdx.x; t < kRangeParts; t += blockDim.x) {
-      pc[t] = 0;
-      cn[t] = 0;
-      s0[t] = 0.0;
-      s1[t] = 0.0;
-      s2[t] = 0.0;
-    }
-  }
-  // buckets in batches of one per thread: run starts, block scan, then the
-  // batch's records, RR per thread in flight (their run lookups and loads
-  // issued before the atomics)
-  constexpr int RR = 4;
-  for (int64_t bb = b_lo; bb < b_hi; bb += blockDim.x) {
-    int64_t nb = b_hi - bb;
-    if (nb > blockDim.x) nb = blockDim.x;
-    unsigned len = 0;
-    if (threadIdx.x < nb) {
-      const int64_t b = bb + threadIdx.x;
-      const unsigned* run = rec.runs + r * rec.run_stride + b;
-      const unsigned s = run[0];
-      len = run[rec.run_stride] - s;
-      start[threadIdx.x] = (unsigned long long)(b * n_slots + s);
-    }
-    unsigned total;
-    const unsigned ex = block_excl_scan(len, wsum, &total);
-    pre[threadIdx.x] = ex;
-    __syncthreads();
-    for (unsigned i0 = threadIdx.x; i0 < total; i0 += RR * blockDim.x) {
-      uint64_t idx[RR];
-      bool ok[RR];
-#pragma unroll
-      for (int u = 0; u < RR; ++u) {
-        const unsigned i = i0 + u * blockDim.x;
-        ok[u] = i < total;
-        int lo = 0, hi = (int)nb - 1;  // last run with pre <= i
-        while (ok[u] && lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (pre[mid] <= i) lo = mid;
-          else hi = mid - 1;
-        }
-        idx[u] = ok[u] ? start[lo] + (i - pre[lo]) : 0;
-      }
-      unsigned long long key[RR];
-      double v0[RR], v1[RR], v2[RR];
-#pragma unroll
-      for (int u = 0; u < RR; ++u) {
-        key[u] = ok[u] ? rec.key[idx[u]] : 0ull;
-        v0[u] = (ok[u] && f0) ? rec.f0[idx[u]] : 0.0;
-        v1[u] = (ok[u] && f1) ? rec.f1[idx[u]] : 0.0;
-        v2[u] = (ok[u] && f2) ? rec.f2[idx[u]] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < RR; ++u) {
-        if (!ok[u]) continue;
-        // a record outside this item's range (malformed workspace): flagged, skipped
-        if ((int64_t)(key[u] >> 32) >= kp.P || (key[u] >> 32) - (uint64_t)p0 >= (uint64_t)kRangeParts) {
-          atomicOr(err, 1u);
-          continue;
-        }
-        if (direct) {
-          const int64_t p = (int64_t)(key[u] >> 32);
-          atomicAdd((unsigned long long*)(acc.privacy_id_count + p), 1ull);
-          if (acc.count) atomicAdd((unsigned long long*)(acc.count + p), (unsigned long long)(uint32_t)key[u]);
-          if (f0) {
-            if (sum_int) atomicAdd((unsigned long long*)acc.sum + p, (unsigned long long)__double_as_longlong(v0[u]));
-            else unsafeAtomicAdd((double*)acc.sum + p, v0[u]);
-          }
-          if (f1) unsafeAtomicAdd(acc.normalized_sum + p, v1[u]);
-          if (f2) unsafeAtomicAdd(acc.normalized_sum_sq + p, v2[u]);
-          continue;
-        }
-        const int lp = (int)((key[u] >> 32) - (uint64_t)p0);
-        atomicAdd(pc + lp, 1u);
-        atomicAdd(cn + lp, (unsigned)key[u]);
-        if (f0) {
-          if (sum_int) atomicAdd((unsigned long long*)(s0 + lp), (unsigned long long)__double_as_longlong(v0[u]));
-          else atomicAdd(s0 + lp, v0[u]);
-        }
-        if (f1) atomicAdd(s1 + lp, v1[u]);
-        if (f2) atomicAdd(s2 + lp, v2[u]);
-      }
-    }
-    __syncthreads();  // pre / start / wsum are reused by the next batch
-  }
-  if (direct) return;
-  int64_t plen = kp.P - p0;
-  if (plen > kRangeParts) plen = kRangeParts;
-  for (int t = threadIdx.x; t < plen; t += blockDim.x) {
-    if (pc[t] == 0) continue;
-    const int64_t p = p0 + t;
-    atomicAdd((unsigned long long*)(acc.privacy_id_count + p), (unsigned long long)pc[t]);
-    if (acc.count) atomicAdd((unsigned long long*)(acc.count + p), (unsigned long long)cn[t]);
-    if (f0) {
-      if (sum_int) atomicAdd((unsigned long long*)acc.sum + p, (unsigned long long)__double_as_longlong(s0[t]));
-      else unsafeAtomicAdd((double*)acc.sum + p, s0[t]);
-    }
-    if (f1) unsafeAtomicAdd(acc.normalized_sum + p, s1[t]);
-    if (f2) unsafeAtomicAdd(acc.normalized_sum_sq + p, s2[t]);
-  }
-}
-
-// ----------------------------------------------------- two-level merge --
-// Records of coarse range r (work item from k_range_plan, buckets [b_lo,
-// b_hi)) in batches of one bucket per thread; visit(idx, ok) for RR records
-// per thread at a time (ok = a real record), then `after()` once per round.
-template <typename V, typename A>
-__device__ __forceinline__ void item_rounds(const KP& kp, const PairRecords& rec, int r, int64_t b_lo, int64_t b_hi,
-                                            unsigned long long* start, unsigned* pre, unsigned* wsum, V&& visit,
-                                            A&& after) {
-  constexpr int RR = 4;
-  const int64_t n_slots = (int64_t)kp.l0 << kp.bucket_bits;
-  for (int64_t bb = b_lo; bb < b_hi; bb += blockDim.x) {
-    int64_t nb = b_hi - bb;
-    if (nb > blockDim.x) nb = blockDim.x;
-    unsigned len = 0;
-    if (threadIdx.x < nb) {
-      const int64_t b = bb + threadIdx.x;
-      const unsigned* run = rec.runs + r * rec.run_stride + b;
-      const unsigned s0 = run[0];
-      len = run[rec.run_stride] - s0;
-      start[threadIdx.x] = (unsigned long long)(b * n_slots + s0);
-    }
-    unsigned total;
-    const unsigned ex = block_excl_scan(len, wsum, &total);
-    pre[threadIdx.x] = ex;
-    __syncthreads();
-    for (unsigned i0 = 0; i0 < total; i0 += RR * blockDim.x) {  // block-uniform trip count
-      uint64_t idx[RR];
-      bool ok[RR];
-#pragma unroll
-      for (int u = 0; u < RR; ++u) {
-        const unsigned i = i0 + threadIdx.x + u * blockDim.x;
-        ok[u] = i < total;
-        int lo = 0, hi = (int)nb - 1;  // last run with pre <= i
-        while (ok[u] && lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (pre[mid] <= i) lo = mid;
-          else hi = mid - 1;
-        }
-        idx[u] = ok[u] ? start[lo] + (i - pre[lo]) : 0;
-      }
-      visit(idx, ok);
-      after();
-    }
-    __syncthreads();  // pre / start / wsum are reused by the next batch
-  }
-}
-
-#ifndef PDP_SPLIT_STAGED
-#define PDP_SPLIT_STAGED 1
-#endif
-constexpr int kFinePerCoarseMax = 1 << 13;  // 2^(range_bits - kRangeBits) <= 2^13 (P < 2^32, 256 coarse ranges)
-
-// fine-range totals: per item an LDS histogram of its records' fine ranges,
-// added to fine_total with one atomic per touched fine range
-__global__ void __launch_bounds__(kSplitThreads) k_split_count(KP kp, PairRecords rec, const uint4* __restrict__ items,
-                                                              const unsigned* __restrict__ n_items,
-                                                              unsigned* __restrict__ fine_total,
-                                                              unsigned* __restrict__ item_hist) {
-  __shared__ unsigned long long start[kSplitThreads];
-  __shared__ unsigned pre[kSplitThreads], wsum[kSplitThreads / 64 + 1];
-  __shared__ unsigned lh[kFinePerCoarseMax];
-  if (blockIdx.x >= *n_items) return;
-  const uint4 it = items[blockIdx.x];
-  if (it.x >> 31) return;  // sentinel
-  const uint4 nx = items[blockIdx.x + 1];
-  if (nx.z == it.z) return;  // empty item
-  const int r = (int)it.x;
-  const int F = 1 << (kp.range_bits - kRangeBits);
-  const int64_t f0 = (int64_t)r << (kp.range_bits - kRangeBits);
-  for (int t = threadIdx.x; t < F; t += blockDim.x) lh[t] = 0;
-  __syncthreads();
-  item_rounds(kp, rec, r, it.y, nx.y, start, pre, wsum,
-              [&](const uint64_t (&idx)[4], const bool (&ok)[4]) {
-                // the four loads unconditional (idx = 0 where !ok), so they
-                // go out together: under the `ok` branch each waited for the last
-                unsigned long long kk[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) kk[u] = rec.key[idx[u]];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  if (!ok[u]) continue;
-                  const uint64_t f = (kk[u] >> (32 + kRangeBits)) - (uint64_t)f0;
-                  if (f < (uint64_t)F) atomicAdd(lh + (int)f, 1u);  // else malformed: k_split_scatter skips it too
-                }
-              },
-              [] {});
-  __syncthreads();
-  // the item's histogram for k_split_scatter, which then reserves its slots
-  // once per fine range instead of once per round
-  for (int t = threadIdx.x; t < F; t += blockDim.x) {
-    const bool in = f0 + t < kp.n_fine_ranges;
-    item_hist[(int64_t)blockIdx.x * F + t] = in ? lh[t] : 0u;
-    if (lh[t] && in) atomicAdd(fine_total + f0 + t, lh[t]);
-  }
-}
-
-// records of an item -> the fine-range-sorted arrays: the item reserves its
-// slots of every fine range once (its histogram from k_split_count, one
-// device atomic per touched fine range), then each record takes the next slot
-// of its fine range from an LDS cursor (a returning LDS atomic) -- no
-// barriers between the batches, so their loads overlap
-__global__ void __launch_bounds__(kSplitThreads) k_split_scatter(KP kp, PairRecords rec, PairRecords stg,
-                                                                const uint4* __restrict__ items,
-                                                                const unsigned* __restrict__ n_items,
-                                                                unsigned* __restrict__ fine_cur,
-                                                                const unsigned* __restrict__ item_hist) {
-  __shared__ unsigned long long start[kSplitThreads];
-  __shared__ unsigned pre[kSplitThreads], wsum[kSplitThreads / 64 + 1];
-  __shared__ unsigned lcur[kFinePerCoarseMax];
-  if (blockIdx.x >= *n_items) return;
-  const uint4 it = items[blockIdx.x];
-  if (it.x >> 31) return;
-  const uint4 nx = items[blockIdx.x + 1];
-  if (nx.z == it.z) return;
-  const int r = (int)it.x;
-  const int F = 1 << (kp.range_bits - kRangeBits);
-  const int64_t f0 = (int64_t)r << (kp.range_bits - kRangeBits);
-  for (int t = threadIdx.x; t < F; t += blockDim.x) {
-    const unsigned c = item_hist[(int64_t)blockIdx.x * F + t];
-    lcur[t] = c ? atomicAdd(fine_cur + f0 + t, c) : 0u;
-  }
-  __syncthreads();
-  item_rounds(kp, rec, r, it.y, nx.y, start, pre, wsum,
-              [&](const uint64_t (&idx)[4], const bool (&ok)[4]) {
-                unsigned long long key[4];
-                double v0[4], v1[4], v2[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  key[u] = ok[u] ? rec.key[idx[u]] : 0ull;
-                  v0[u] = (ok[u] && stg.f0) ? rec.f0[idx[u]] : 0.0;
-                  v1[u] = (ok[u] && stg.f1) ? rec.f1[idx[u]] : 0.0;
-                  v2[u] = (ok[u] && stg.f2) ? rec.f2[idx[u]] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  const uint64_t fu = (key[u] >> (32 + kRangeBits)) - (uint64_t)f0;
-                  // a malformed record is skipped, as k_split_count leaves it uncounted
-                  if (!ok[u] || fu >= (uint64_t)F || f0 + (int64_t)fu >= kp.n_fine_ranges) continue;
-                  const uint64_t o = atomicAdd(lcur + (int)fu, 1u);
-                  stg.key[o] = key[u];
-                  if (stg.f0) stg.f0[o] = v0[u];
-                  if (stg.f1) stg.f1[o] = v1[u];
-                  if (stg.f2) stg.f2[o] = v2[u];
-                }
-              },
-              [] {});
-}
-
-// k_split_scatter for coarse ranges of <= kSplitStageFan fine ranges (C4 /
-// C5: 32): each round's records are counting-sorted by fine range in LDS
-// first, so a fine range's records leave as one contiguous run (~32 per
-// round) instead of one scattered 8-byte store per record and array
-constexpr int kSplitStageFan = 256;
-constexpr int kSplitStageRows = 4 * kSplitThreads;  // item_rounds' RR records per thread
-__global__ void __launch_bounds__(kSplitThreads) k_split_scatter_staged(KP kp, PairRecords rec, PairRecords stg,
-                                                                       const uint4* __restrict__ items,
-                                                                       const unsigned* __restrict__ n_items,
-                                                                       unsigned* __restrict__ fine_cur,
-                                                                       const unsigned* __restrict__ item_hist) {
-  __shared__ unsigned long long start[kSplitThreads];
-  __shared__ unsigned pre[kSplitThreads], wsum[kSplitThreads / 64 + 1];
-  __shared__ unsigned lcur[kSplitStageFan], hist[kSplitStageFan], hstart[kSplitStageFan], gbase[kSplitStageFan];
-  __shared__ unsigned long long skey[kSplitStageRows];
-  __shared__ double sf0[kSplitStageRows], sf1[kSplitStageRows], sf2[kSplitStageRows];
-  __shared__ uint8_t sdest[kSplitStageRows];
-  if (blockIdx.x >= *n_items) return;
-  const uint4 it = items[blockIdx.x];
-  if (it.x >> 31) return;
-  const uint4 nx = items[blockIdx.x + 1];
-  if (nx.z == it.z) return;
-  const int r = (int)it.x;
-  const int F = 1 << (kp.range_bits - kRangeBits);  // <= kSplitStageFan (host-checked)
-  const int64_t f0 = (int64_t)r << (kp.range_bits - kRangeBits);
-  for (int t = threadIdx.x; t < F; t += blockDim.x) {
-    const unsigned c = item_hist[(int64_t)blockIdx.x * F + t];
-    lcur[t] = c ? atomicAdd(fine_cur + f0 + t, c) : 0u;
-    hist[t] = 0;
-  }
-  __syncthreads();
-  item_rounds(kp, rec, r, it.y, nx.y, start, pre, wsum,
-              [&](const uint64_t (&idx)[4], const bool (&ok)[4]) {
-                unsigned long long key[4];
-                double v0[4], v1[4], v2[4];
-                int fu[4];
-                unsigned rk[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  key[u] = ok[u] ? rec.key[idx[u]] : 0ull;
-                  v0[u] = (ok[u] && stg.f0) ? rec.f0[idx[u]] : 0.0;
-                  v1[u] = (ok[u] && stg.f1) ? rec.f1[idx[u]] : 0.0;
-                  v2[u] = (ok[u] && stg.f2) ? rec.f2[idx[u]] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  const uint64_t f = (key[u] >> (32 + kRangeBits)) - (uint64_t)f0;
-                  // a malformed record is skipped, as k_split_count leaves it uncounted
-                  fu[u] = ok[u] && f < (uint64_t)F && f0 + (int64_t)f < kp.n_fine_ranges ? (int)f : -1;
-                  rk[u] = fu[u] >= 0 ? atomicAdd(hist + fu[u], 1u) : 0u;
-                }
-                __syncthreads();
-                if (threadIdx.x < 64) {  // run starts in the stage; the runs' output positions
-                  const int lane = threadIdx.x;
-                  unsigned carry = 0;
-                  for (int b0 = 0; b0 < F; b0 += 64) {
-                    const unsigned hv = b0 + lane < F ? hist[b0 + lane] : 0u;
-                    unsigned incl = hv;
-                    for (int o = 1; o < 64; o <<= 1) {
-                      const unsigned up = __shfl_up(incl, o, 64);
-                      if (lane >= o) incl += up;
-                    }
-                    if (b0 + lane < F) {
-                      hstart[b0 + lane] = carry + incl - hv;
-                      gbase[b0 + lane] = lcur[b0 + lane];
-                      lcur[b0 + lane] += hv;
-                    }
-                    carry += __shfl(incl, 63, 64);
-                  }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  if (fu[u] < 0) continue;
-                  const unsigned sl = hstart[fu[u]] + rk[u];
-                  skey[sl] = key[u];
-                  sf0[sl] = v0[u];
-                  sf1[sl] = v1[u];
-                  sf2[sl] = v2[u];
-                  sdest[sl] = (uint8_t)fu[u];
-                }
-                __syncthreads();
-                const unsigned n = hstart[F - 1] + hist[F - 1];
-                for (unsigned i = threadIdx.x; i < n; i += blockDim.x) {
-                  const int f = sdest[i];
-                  const uint64_t o = (uint64_t)gbase[f] + (i - hstart[f]);
-                  stg.key[o] = skey[i];
-                  if (stg.f0) stg.f0[o] = sf0[i];
-                  if (stg.f1) stg.f1[o] = sf1[i];
-                  if (stg.f2) stg.f2[o] = sf2[i];
-                }
-                __syncthreads();
-                for (int t = threadIdx.x; t < F; t += blockDim.x) hist[t] = 0;
-                __syncthreads();
-              },
-              [] {});
-}
-
-// fine work items: fine range f's records [start_f, start_f+1) in chunks of
-// kRangeChunk, appended at a base taken with one atomic (any order)
-__global__ void __launch_bounds__(kBlock) k_fine_plan(KP kp, const unsigned* __restrict__ fine_start,
-                                                      uint4* __restrict__ items, unsigned* __restrict__ n_items) {
-  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= kp.n_fine_ranges) return;
-  const unsigned s0 = fine_start[f], s1 = fine_start[f + 1];
-  if (s1 <= s0) return;
-  const unsigned C = (unsigned)kRangeChunk;
-  const unsigned k = (s1 - s0 + C - 1) / C;
-  const unsigned base = atomicAdd(n_items, k);
-  for (unsigned j = 0; j < k; ++j) {
-    const unsigned a = s0 + j * C;
-    items[base + j] = make_uint4((unsigned)f, a, (s1 - a < C ? s1 - a : C), 0u);
-  }
-}
-
-// one workgroup per fine item: contiguous records of one 2^kRangeBits range,
-// summed in LDS (or added directly when few), then coalesced atomics
-__global__ void __launch_bounds__(kReduceThreads) k_fine_reduce(KP kp, PairRecords stg, const uint4* __restrict__ items,
-                                                              const unsigned* __restrict__ n_items,
-                                                              pdp_partition_accumulators acc, unsigned* err) {
-  extern __shared__ unsigned long long smem[];
-  double* s0 = (double*)smem;
-  double* s1 = s0 + kRangeParts;
-  double* s2 = s1 + kRangeParts;
-  unsigned* pc = (unsigned*)(s2 + kRangeParts);
-  unsigned* cn = pc + kRangeParts;
-  if (blockIdx.x >= *n_items) return;
-  const uint4 it = items[blockIdx.x];
-  const int64_t p0 = (int64_t)it.x << kRangeBits;
-  const uint64_t a = it.y;
-  const unsigned len = it.z;
-  const int flags = kp.clip.flags;
-  const bool f0 = flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION), f1 = flags & PDP_ACC_NSUM,
-             f2 = flags & PDP_ACC_NSUM2, sum_int = flags & PDP_SUM_INT;
-  const bool direct = len < kRangeDirect;
-  if (!direct) {
-    for (int t = threadIdx.x; t < kRangeParts; t += blockDim.x) {
-      pc[t] = 0;
-      cn[t] = 0;
-      s0[t] = 0.0;
-      s1[t] = 0.0;
-      s2[t] = 0.0;
-    }
-    __syncthreads();
-  }
-  // RB records per thread loaded together, then summed
-  constexpr int RB = 4;
-  for (unsigned i0 = threadIdx.x; i0 < len; i0 += RB * blockDim.x) {
-    unsigned long long kk[RB];
-    double w0[RB], w1[RB], w2[RB];
-#pragma unroll
-    for (int u = 0; u < RB; ++u) {
-      const unsigned i = i0 + u * blockDim.x;
-      const uint64_t o = a + (i < len ? i : 0u);
-      kk[u] = i < len ? stg.key[o] : ~0ull;
-      w0[u] = (i < len && f0) ? stg.f0[o] : 0.0;
-      w1[u] = (i < len && f1) ? stg.f1[o] : 0.0;
-      w2[u] = (i < len && f2) ? stg.f2[o] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < RB; ++u) {
-      if (i0 + u * blockDim.x >= len) continue;
-      const unsigned long long key = kk[u];
-      if ((int64_t)(key >> 32) >= kp.P || (key >> 32) - (uint64_t)p0 >= (uint64_t)kRangeParts) {  // malformed
-        atomicOr(err, 1u);
-        continue;
-      }
-      const double v0 = w0[u], v1 = w1[u], v2 = w2[u];
-      if (direct) {
-        const int64_t p = (int64_t)(key >> 32);
-        atomicAdd((unsigned long long*)(acc.privacy_id_count + p), 1ull);
-        if (acc.count) atomicAdd((unsigned long long*)(acc.count + p), (unsigned long long)(uint32_t)key);
-        if (f0) {
-          if (sum_int) atomicAdd((unsigned long long*)acc.sum + p, (unsigned long long)__double_as_longlong(v0));
-          else unsafeAtomicAdd((double*)acc.sum + p, v0);
-        }
-        if (f1) unsafeAtomicAdd(acc.normalized_sum + p, v1);
-        if (f2) unsafeAtomicAdd(acc.normalized_sum_sq + p, v2);
-        continue;
-      }
-      const int lp = (int)((key >> 32) - (uint64_t)p0);
-      atomicAdd(pc + lp, 1u);
-      atomicAdd(cn + lp, (unsigned)key);
-      if (f0) {
-        if (sum_int) atomicAdd((unsigned long long*)(s0 + lp), (unsigned long long)__double_as_longlong(v0));
-        else atomicAdd(s0 + lp, v0);
-      }
-      if (f1) atomicAdd(s1 + lp, v1);
-      if (f2) atomicAdd(s2 + lp, v2);
-    }
-  }
-  if (direct) return;
-  __syncthreads();
-  int64_t plen = kp.P - p0;
-  if (plen > kRangeParts) plen = kRangeParts;
-  for (int t = threadIdx.x; t < plen; t += blockDim.x) {
-    if (pc[t] == 0) continue;
-    const int64_t p = p0 + t;
-    atomicAdd((unsigned long long*)(acc.privacy_id_count + p), (unsigned long long)pc[t]);
-    if (acc.count) atomicAdd((unsigned long long*)(acc.count + p), (unsigned long long)cn[t]);
-    if (f0) {
-      if (sum_int) atomicAdd((unsigned long long*)acc.sum + p, (unsigned long long)__double_as_longlong(s0[t]));
-      else unsafeAtomicAdd((double*)acc.sum + p, s0[t]);
-    }
-    if (f1) unsafeAtomicAdd(acc.normalized_sum + p, s1[t]);
-    if (f2) unsafeAtomicAdd(acc.normalized_sum_sq + p, s2[t]);
-  }
-}
-constexpr size_t kFineLds = kRangeParts * (3 * 8 + 2 * 4);
-
-// exclusive scan of u32 counts[0..n) in place, total -> counts[n]
-__global__ void __launch_bounds__(kBlock) k_scan_chunks(const unsigned* __restrict__ v, int64_t n,
-                                                        unsigned* __restrict__ chunk_sums) {
-  __shared__ unsigned red[kBlock / 64];
-  const int64_t base = (int64_t)blockIdx.x * kScanChunk + (int64_t)threadIdx.x * kScanItems;
-  unsigned s = 0;
-#pragma unroll
-  for (int t = 0; t < kScanItems; ++t)
-    if (base + t < n) s += v[base + t];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-    for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-    chunk_sums[blockIdx.x] = t;
-  }
-}
-
-__global__ void __launch_bounds__(kBlock) k_scan_top(unsigned* chunk_sums, int64_t n_chunks) {
-  __shared__ unsigned part[kBlock];
-  __shared__ unsigned carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < n_chunks; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const unsigned x = i < n_chunks ? chunk_sums[i] : 0;
-    part[threadIdx.x] = x;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-      const unsigned t = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < n_chunks) chunk_sums[i] = carry + part[threadIdx.x] - x;
-    __syncthreads();
-    if (threadIdx.x == kBlock - 1) carry += part[kBlock - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) chunk_sums[n_chunks] = carry;
-}
-
-__global__ void __launch_bounds__(kBlock) k_scan_apply(unsigned* v, int64_t n,
-                                                       const unsigned* __restrict__ chunk_sums,
-                                                       int64_t n_chunks) {
-  __shared__ unsigned part[kBlock];
-  const int64_t base = (int64_t)blockIdx.x * kScanChunk + (int64_t)threadIdx.x * kScanItems;
-  unsigned loc[kScanItems];
-  unsigned s = 0;
-#pragma unroll
-  for (int t = 0; t < kScanItems; ++t) {
-    loc[t] = base + t < n ? v[base + t] : 0;
-    s += loc[t];
-  }
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {
-    const unsigned t = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-    __syncthreads();
-    part[threadIdx.x] += t;
-    __syncthreads();
-  }
-  unsigned run = chunk_sums[blockIdx.x] + part[threadIdx.x] - s;
-#pragma unroll
-  for (int t = 0; t < kScanItems; ++t) {
-    if (base + t < n) v[base + t] = run;
-    run += loc[t];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) v[n] = chunk_sums[n_chunks];
-}
-
-// the same scan in one launch for n <= kScanSmallMax (bucket offsets: C2 1,954
-// and C3 4,928 entries), 16 consecutive entries per thread
-constexpr int kScanSmallThreads = 1024;
-constexpr int64_t kScanSmallMax = (int64_t)kScanSmallThreads * kScanItems;
-__global__ void __launch_bounds__(kScanSmallThreads) k_scan_small(unsigned* v, int64_t n) {
-  __shared__ unsigned wsum[kScanSmallThreads / 64 + 1];
-  const int64_t base = (int64_t)threadIdx.x * kScanItems;
-  unsigned loc[kScanItems];
-  unsigned s = 0;
-#pragma unroll
-  for (int t = 0; t < kScanItems; ++t) {
-    loc[t] = base + t < n ? v[base + t] : 0u;
-    s += loc[t];
-  }
-  unsigned total;
-  unsigned run = block_excl_scan(s, wsum, &total);
-#pragma unroll
-  for (int t = 0; t < kScanItems; ++t) {
-    if (base + t < n) v[base + t] = run;
-    run += loc[t];
-  }
-  if (threadIdx.x == 0) v[n] = total;
-}
-
-}  // namespace
-
-int64_t scan_chunk_sums_len(int64_t n) { return (n + kScanChunk - 1) / kScanChunk + 1; }
-
-int scan_u32(unsigned* v, int64_t n, unsigned* chunk_sums, hipStream_t st) {
-  const int64_t n_chunks = (n + kScanChunk - 1) / kScanChunk;
-  if (n_chunks == 0) return set_error(PDP_E_INVALID, "scan of an empty array");
-  if (n <= kScanSmallMax) {
-    PDP_PROF_BEGIN("k_scan_small", st);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(kScanSmallThreads), 0, st, v, n);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    return PDP_OK;
-  }
-  PDP_PROF_BEGIN("k_scan_chunks", st);
-  hipLaunchKernelGGL(k_scan_chunks, dim3((unsigned)n_chunks), dim3(kBlock), 0, st, v, n, chunk_sums);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_scan_top", st);
-  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kBlock), 0, st, chunk_sums, n_chunks);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_scan_apply", st);
-  hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)n_chunks), dim3(kBlock), 0, st, v, n, chunk_sums, n_chunks);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
-}
-
-namespace {
 
 // ---------------------------------------------------------- launchers --
-template <int VK, bool KA>
-int launch_global_rows(const KP& kp, hipStream_t st, const int64_t* pid, const int64_t* pk, const void* value,
-                       const uint8_t* allowed, char* ws, const Ws& w) {
-  PDP_PROF_BEGIN("k_pair_rows", st);
-  hipLaunchKernelGGL((k_pair_rows<VK, KA>), dim3(grid_for(kp.n)), dim3(kBlock), 0, st, kp, pid, pk, value,
-                     allowed, (const unsigned long long*)(ws + w.sketch), (unsigned*)(ws + w.cnt),
-                     KA ? nullptr : (unsigned long long*)(ws + w.rows), KA ? (double*)(ws + w.fsum) : nullptr,
-                     KA ? (double*)(ws + w.nsum) : nullptr, KA ? (double*)(ws + w.nsum2) : nullptr);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+int launch_global_rows(const pdp_bound_config* cfg, const KP& kp, hipStream_t st, const int64_t* pid,
+                       const int64_t* pk, const void* value, const uint8_t* allowed, char* ws, const Ws& w) {
+  return with_value(cfg->value_kind, cfg->linf == 0, [&](auto vk, auto ka) {
+    constexpr bool KA = decltype(ka)::value;
+    return launch("k_pair_rows", k_pair_rows<decltype(vk)::value, KA>, dim3(grid_for(kp.n)), dim3(kBlock), 0, st, kp,
+                  pid, pk, value, allowed, (const unsigned long long*)(ws + w.sketch), (unsigned*)(ws + w.cnt),
+                  KA ? nullptr : (unsigned long long*)(ws + w.rows), KA ? (double*)(ws + w.fsum) : nullptr,
+                  KA ? (double*)(ws + w.nsum) : nullptr, KA ? (double*)(ws + w.nsum2) : nullptr);
+  });
 }
 
-template <int VK, bool KA>
-int launch_global_reduce(const KP& kp, hipStream_t st, const void* value, const char* ws, const Ws& w,
-                         const pdp_partition_accumulators& acc) {
-  PDP_PROF_BEGIN("k_reduce_pairs", st);
-  hipLaunchKernelGGL((k_reduce_pairs<VK, KA>), dim3(grid_for(kp.U * kp.l0)), dim3(kBlock), 0, st, kp, value,
-                     (const unsigned long long*)(ws + w.sketch), (const unsigned*)(ws + w.cnt),
-                     KA ? nullptr : (const unsigned long long*)(ws + w.rows),
-                     KA ? (const double*)(ws + w.fsum) : nullptr, KA ? (const double*)(ws + w.nsum) : nullptr,
-                     KA ? (const double*)(ws + w.nsum2) : nullptr, acc);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+int launch_global_reduce(const pdp_bound_config* cfg, const KP& kp, hipStream_t st, const void* value,
+                         const char* ws, const Ws& w, const pdp_partition_accumulators& acc) {
+  return with_value(cfg->value_kind, cfg->linf == 0, [&](auto vk, auto ka) {
+    constexpr bool KA = decltype(ka)::value;
+    return launch("k_reduce_pairs", k_reduce_pairs<decltype(vk)::value, KA>, dim3(grid_for(kp.U * kp.l0)),
+                  dim3(kBlock), 0, st, kp, value, (const unsigned long long*)(ws + w.sketch),
+                  (const unsigned*)(ws + w.cnt), KA ? nullptr : (const unsigned long long*)(ws + w.rows),
+                  KA ? (const double*)(ws + w.fsum) : nullptr, KA ? (const double*)(ws + w.nsum) : nullptr,
+                  KA ? (const double*)(ws + w.nsum2) : nullptr, acc);
+  });
 }
+
+int64_t device_cus();  // compute units of the current device
+
 
 // where a bucket launch marks unresolved ids (the main launch: the first
 // bitmap / list / counters; the band's fix-up launch: the second ones, only
@@ -3807,8 +2956,6 @@ struct Marks {
   unsigned long long* fix_rec;
 };
 
-int64_t device_cus();  // compute units of the current device
-
 template <int VK, bool KA>
 int launch_bucket_kernel(const KP& kp, const Plan& p, hipStream_t st, const void* keys, const unsigned* rows,
                          const unsigned* offsets, const void* value, const pdp_partition_accumulators& acc,
@@ -3816,49 +2963,20 @@ int launch_bucket_kernel(const KP& kp, const Plan& p, hipStream_t st, const void
                          const unsigned* blist = nullptr) {
   const bool ranges = p.merge == PDP_MERGE_RANGES;
   // PACKED: COMPACT records from level 2 on; PACKED_WIDE: WIDE ones; PACKED64: its own
-  const int kind = rec_of(p.key_format);
-  const void* kern =
-      kind == kRecCompact ? (ranges ? (const void*)k_bucket_bound<VK, KA, true, kRecCompact>
-                                   : (const void*)k_bucket_bound<VK, KA, false, kRecCompact>)
-      : kind == kRecWide  ? (ranges ? (const void*)k_bucket_bound<VK, KA, true, kRecWide>
-                                   : (const void*)k_bucket_bound<VK, KA, false, kRecWide>)
-                         : (ranges ? (const void*)k_bucket_bound<VK, KA, true, kRecP64>
-                                   : (const void*)k_bucket_bound<VK, KA, false, kRecP64>);
-  PDP_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-  void* cand_key = ws + w.cand_key;
-  unsigned* cand_idx = (unsigned*)(ws + w.cand_idx);
-  unsigned* unres_bits = mk.bits;
-  unsigned* unres_list = mk.list;
-  unsigned* sctl = mk.sctl;
-  unsigned* err = (unsigned*)(ws + w.err);
-  unsigned long long* fix_rec = mk.fix_rec;
-  const unsigned* prev = mk.prev;
-  void* args[] = {(void*)&kp,       (void*)&keys,       (void*)&rows,       (void*)&offsets,
-                  (void*)&value,    (void*)&acc,        (void*)&rec,        (void*)&cand_key,
-                  (void*)&cand_idx, (void*)&unres_bits, (void*)&unres_list, (void*)&sctl,
-                  (void*)&err,      (void*)&fix_rec,    (void*)&prev,       (void*)&blist};
-  // a listed launch (fix-ups): a persistent grid of one workgroup per CU (the
-  // bucket LDS allows no more) looping over the listed buckets
-  const int64_t grid = blist != nullptr ? std::min<int64_t>(p.n_buckets, device_cus()) : p.n_buckets;
-  PDP_PROF_BEGIN(name, st);
-  PDP_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3((unsigned)p.bucket_threads), args,
-                                (size_t)p.lds_bytes, st));
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
-}
-
-PairRecords pair_records(char* ws, const Ws& w, const Plan& p) {
-  PairRecords rec{};
-  if (w.runs) {
-    rec.runs = (unsigned*)(ws + w.runs);
-    rec.run_stride = p.buckets_out;
-    rec.key = (unsigned long long*)(ws + w.rec_key);
-    rec.f0 = w.rec_f0 ? (double*)(ws + w.rec_f0) : nullptr;
-    rec.f1 = w.rec_f1 ? (double*)(ws + w.rec_f1) : nullptr;
-    rec.f2 = w.rec_f2 ? (double*)(ws + w.rec_f2) : nullptr;
-  }
-  return rec;
+  return with_rec(rec_of(p.key_format), [&](auto kind) {
+    constexpr int REC = decltype(kind)::value;
+    using K = RecKey<REC == kRecCompact>;
+    const auto kern = ranges ? k_bucket_bound<VK, KA, true, REC> : k_bucket_bound<VK, KA, false, REC>;
+    const int rc = allow_dynamic_lds(kern, (size_t)p.lds_bytes);
+    if (rc != PDP_OK) return rc;
+    // a listed launch (fix-ups): a persistent grid of one workgroup per CU (the
+    // bucket LDS allows no more) looping over the listed buckets
+    const int64_t grid = blist != nullptr ? std::min<int64_t>(p.n_buckets, device_cus()) : p.n_buckets;
+    return launch(name, kern, dim3((unsigned)grid), dim3((unsigned)p.bucket_threads), (size_t)p.lds_bytes, st, kp,
+                  (const K*)keys, rows, offsets, value, acc, rec, (K*)(ws + w.cand_key),
+                  (unsigned*)(ws + w.cand_idx), mk.bits, mk.list, mk.sctl, (unsigned*)(ws + w.err), mk.fix_rec,
+                  mk.prev, blist);
+  });
 }
 
 // Sampling (every bucket kernel): the main launch over the level-2 records;
@@ -3872,9 +2990,9 @@ PairRecords pair_records(char* ws, const Ws& w, const Plan& p) {
 // Every step past the main launch reads its counts on the device, so an
 // empty fix-up costs a few near-empty launches and no host round trip.
 template <int VK, bool KA>
-int launch_buckets(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
-                   const uint8_t* allowed, const void* value, const pdp_partition_accumulators& acc, char* ws,
-                   const Ws& w) {
+int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
+                      const uint8_t* allowed, const void* value, const pdp_partition_accumulators& acc, char* ws,
+                      const Ws& w) {
   const PairRecords rec = pair_records(ws, w, p);
   unsigned long long* fix_rec = (unsigned long long*)(ws + w.fix_rec);  // level-1 blocks are dead
   Marks m1{w.unres_bits ? (unsigned*)(ws + w.unres_bits) : nullptr,
@@ -3883,36 +3001,24 @@ int launch_buckets(const KP& kp, const Plan& p, hipStream_t st, const int64_t* p
   int rc = launch_bucket_kernel<VK, KA>(kp, p, st, ws + w.keys2, (const unsigned*)(ws + w.rows2),
                                         (const unsigned*)(ws + w.counts), value, acc, rec, ws, w, "k_bucket_bound", m1);
   if (rc != PDP_OK || !p.sieve) return rc;
-  const int kind = rec_of(p.key_format);
   const int64_t n_slots = (int64_t)kp.l0 << kp.bucket_bits;
   // one fix-up: rows listed in fix_rec (sctl[1] of them) -> exact test ->
   // bucket order -> a bucket launch over them into record segment `seg`
   auto fixup = [&](unsigned* bits, unsigned* sctl, unsigned* fix_cnt, unsigned* fix_cur, int seg, const Marks& mk,
                    int mark, const char* name) -> int {
-    PDP_PROF_BEGIN("k_fix_filter", st);
     unsigned* blist = (unsigned*)(ws + w.fix_blist);
-    hipLaunchKernelGGL(k_fix_filter, dim3(grid_for(kp.n, 1024)), dim3(kBlock), 0, st, kp, (const unsigned*)bits,
-                       (const unsigned*)sctl, fix_rec, fix_cnt, (unsigned*)(ws + w.err), blist);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    int r = scan_u32(fix_cnt, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);  // -> starts
+    int r = launch("k_fix_filter", k_fix_filter, dim3(grid_for(kp.n, 1024)), dim3(kBlock), 0, st, kp, bits, sctl,
+                   fix_rec, fix_cnt, (unsigned*)(ws + w.err), blist);
     if (r != PDP_OK) return r;
-    const unsigned fix_grid = grid_for(kp.n, 2048);
-    PDP_PROF_BEGIN("k_fix_scatter", st);
-    if (kind == kRecCompact)
-      hipLaunchKernelGGL(k_fix_scatter<kRecCompact>, dim3(fix_grid), dim3(kBlock), 0, st, kp, pk, allowed,
-                         (const unsigned long long*)fix_rec, (const unsigned*)sctl, (const unsigned*)fix_cnt, fix_cur,
-                         (uint32_t*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
-    else if (kind == kRecWide)
-      hipLaunchKernelGGL(k_fix_scatter<kRecWide>, dim3(fix_grid), dim3(kBlock), 0, st, kp, pk, allowed,
-                         (const unsigned long long*)fix_rec, (const unsigned*)sctl, (const unsigned*)fix_cnt, fix_cur,
-                         (unsigned long long*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
-    else
-      hipLaunchKernelGGL(k_fix_scatter<kRecP64>, dim3(fix_grid), dim3(kBlock), 0, st, kp, pk, allowed,
-                         (const unsigned long long*)fix_rec, (const unsigned*)sctl, (const unsigned*)fix_cnt, fix_cur,
-                         (unsigned long long*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
+    r = scan_u32(fix_cnt, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);  // -> starts
+    if (r != PDP_OK) return r;
+    r = with_rec(rec_of(p.key_format), [&](auto kind) {
+      constexpr int REC = decltype(kind)::value;
+      return launch("k_fix_scatter", k_fix_scatter<REC>, dim3(grid_for(kp.n, 2048)), dim3(kBlock), 0, st, kp, pk,
+                    allowed, fix_rec, sctl, fix_cnt, fix_cur, (RecKey<REC == kRecCompact>*)(ws + w.keys2),
+                    (unsigned*)(ws + w.rows2));
+    });
+    if (r != PDP_OK) return r;
     KP kf = kp;
     kf.sieve_mark = mark;
     kf.sieve_emit = 0;
@@ -3926,128 +3032,51 @@ int launch_buckets(const KP& kp, const Plan& p, hipStream_t st, const int64_t* p
     // buckets with rows are listed (k_fix_buckets, which also writes the
     // empty ones' runs and marks) and run on 512 threads (the kernel sizes its
     // queues from blockDim)
-    PDP_PROF_BEGIN("k_fix_buckets", st);
-    hipLaunchKernelGGL(k_fix_buckets, dim3(grid_for(p.n_buckets), kFixRunRows), dim3(kBlock), 0, st, kf,
-                       (const unsigned*)fix_cnt,
-                       p.merge == PDP_MERGE_RANGES ? fr.runs : nullptr, fr.run_stride, blist,
-                       mark ? mk.prev : nullptr, mk.bits, mk.list, mk.sctl);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
+    r = launch("k_fix_buckets", k_fix_buckets, dim3(grid_for(p.n_buckets), kFixRunRows), dim3(kBlock), 0, st, kf,
+               fix_cnt, p.merge == PDP_MERGE_RANGES ? fr.runs : nullptr, fr.run_stride, blist,
+               mark ? mk.prev : nullptr, mk.bits, mk.list, mk.sctl);
+    if (r != PDP_OK) return r;
     Plan pf = p;
     if (p.merge != PDP_MERGE_RANGES || p.n_ranges <= kBucketThreads / 2) pf.bucket_threads = kBucketThreads / 2;
     return launch_bucket_kernel<VK, KA>(kf, pf, st, ws + w.keys2, (const unsigned*)(ws + w.rows2),
                                         (const unsigned*)fix_cnt, value, acc, fr, ws, w, name, mk, blist);
   };
   auto rescan = [&](const unsigned* bits, const unsigned* list, unsigned* sctl) {
-    PDP_PROF_BEGIN("k_sieve_rescan", st);
-    if (kp.keys_vec)
-      hipLaunchKernelGGL(k_sieve_rescan<true>, dim3(kRescanBlocks), dim3(kRescanThreads), 0, st, kp, pid, bits, list,
-                         sctl, fix_rec);
-    else
-      hipLaunchKernelGGL(k_sieve_rescan<false>, dim3(kRescanBlocks), dim3(kRescanThreads), 0, st, kp, pid, bits, list,
-                         sctl, fix_rec);
-    PDP_PROF_END(st);
+    return launch("k_sieve_rescan", kp.keys_vec ? k_sieve_rescan<true> : k_sieve_rescan<false>, dim3(kRescanBlocks),
+                  dim3(kRescanThreads), 0, st, kp, pid, bits, list, sctl, fix_rec);
   };
   unsigned* sctl = (unsigned*)(ws + w.sctl);
   unsigned* fix_cnt = (unsigned*)(ws + w.fix_cnt);
   unsigned* fix_cur = (unsigned*)(ws + w.fix_cur);
   const Marks none{m1.bits, m1.list, m1.sctl, nullptr, nullptr};
   if (!p.band) {
-    rescan(m1.bits, m1.list, sctl);
-    PDP_HIP_CHECK(hipGetLastError());
+    rc = rescan(m1.bits, m1.list, sctl);
+    if (rc != PDP_OK) return rc;
     return fixup(m1.bits, sctl, fix_cnt, fix_cur, 1, none, 0, "k_bucket_fix");
   }
   // the band: its lists (Bloom filter unless too many ids) -> fix-up launch
   // that marks the ids still unresolved -> their rescan -> a third launch
-  PDP_PROF_BEGIN("k_band_scan", st);
-  hipLaunchKernelGGL(k_band_scan, dim3(kRescanBlocks), dim3(kRescanThreads), 0, st, kp,
-                       (const unsigned long long*)(ws + w.band), (const unsigned*)(ws + w.band_cnt),
-                       (const unsigned*)m1.bits, (const unsigned*)m1.list, sctl, fix_rec);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
+  rc = launch("k_band_scan", k_band_scan, dim3(kRescanBlocks), dim3(kRescanThreads), 0, st, kp,
+              (const unsigned long long*)(ws + w.band), (const unsigned*)(ws + w.band_cnt), m1.bits, m1.list, sctl,
+              fix_rec);
+  if (rc != PDP_OK) return rc;
   unsigned* sctl2 = (unsigned*)(ws + w.sctl2);
   const Marks m2{(unsigned*)(ws + w.unres2_bits), (unsigned*)(ws + w.unres2_list), sctl2, m1.bits, nullptr};
   rc = fixup(m1.bits, sctl, fix_cnt, fix_cur, 1, m2, 1, "k_bucket_fix");
   if (rc != PDP_OK) return rc;
-  rescan(m2.bits, m2.list, sctl2);
-  PDP_HIP_CHECK(hipGetLastError());
+  rc = rescan(m2.bits, m2.list, sctl2);
+  if (rc != PDP_OK) return rc;
   return fixup(m2.bits, sctl2, (unsigned*)(ws + w.fix_cnt2), (unsigned*)(ws + w.fix_cur2), 2, m2, 0, "k_bucket_fix2");
 }
 
-// PDP_MERGE_RANGES: the pair records of every bucket (p.buckets_out of them)
-// summed per partition
-int launch_merge(const KP& kp0, const Plan& p, hipStream_t st, char* ws, const Ws& w,
-                 const pdp_partition_accumulators& acc) {
-  KP kp = kp0;
-  kp.n_buckets = p.buckets_out;
-  const PairRecords rec = pair_records(ws, w, p);
-  unsigned* err = (unsigned*)(ws + w.err);
-  {
-    PDP_HIP_CHECK(hipFuncSetAttribute((const void*)k_range_reduce, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kRangeLds));
-    uint4* items = (uint4*)(ws + w.rr_items);
-    unsigned* n_items = (unsigned*)(ws + w.rr_count);
-    PDP_HIP_CHECK(hipMemsetAsync(n_items, 0, 4, st));
-    PDP_PROF_BEGIN("k_range_plan", st);
-    const unsigned* last_ids = p.band ? (const unsigned*)(ws + w.sctl2) : nullptr;
-    hipLaunchKernelGGL(k_range_plan, dim3((unsigned)p.n_ranges), dim3(kRangeThreads), 0, st, kp,
-                       (const unsigned*)rec.runs, items, n_items, last_ids, (int64_t)p.n_buckets);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    if (!p.two_level) {
-      PDP_PROF_BEGIN("k_range_reduce", st);
-      hipLaunchKernelGGL(k_range_reduce, dim3((unsigned)p.n_groups), dim3(kReduceThreads), kRangeLds, st, kp, rec,
-                         (const uint4*)items, (const unsigned*)n_items, acc, err);
-      PDP_PROF_END(st);
-      PDP_HIP_CHECK(hipGetLastError());
-      return PDP_OK;
-    }
-    // two-level: coarse items -> fine-range totals -> starts -> records
-    // re-sorted by fine range -> fine items -> LDS sums
-    unsigned* fine_total = (unsigned*)(ws + w.fine_total);
-    unsigned* fine_cur = (unsigned*)(ws + w.fine_cur);
-    PairRecords stg{};
-    stg.key = (unsigned long long*)(ws + w.stg_key);
-    stg.f0 = w.stg_f0 ? (double*)(ws + w.stg_f0) : nullptr;
-    stg.f1 = w.stg_f1 ? (double*)(ws + w.stg_f1) : nullptr;
-    stg.f2 = w.stg_f2 ? (double*)(ws + w.stg_f2) : nullptr;
-    PDP_HIP_CHECK(hipMemsetAsync(fine_total, 0, (uint64_t)(p.n_fine + 1) * 4, st));
-    PDP_PROF_BEGIN("k_split_count", st);
-    unsigned* item_hist = (unsigned*)(ws + w.item_hist);
-    hipLaunchKernelGGL(k_split_count, dim3((unsigned)p.n_groups), dim3(kSplitThreads), 0, st, kp, rec,
-                       (const uint4*)items, (const unsigned*)n_items, fine_total, item_hist);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    const int rc = scan_u32(fine_total, p.n_fine, (unsigned*)(ws + w.fine_chunks), st);
-    if (rc != PDP_OK) return rc;
-    PDP_HIP_CHECK(hipMemcpyAsync(fine_cur, fine_total, (uint64_t)p.n_fine * 4, hipMemcpyDeviceToDevice, st));
-    PDP_PROF_BEGIN("k_split_scatter", st);
-    if ((1 << (kp.range_bits - kRangeBits)) <= kSplitStageFan && PDP_SPLIT_STAGED)
-      hipLaunchKernelGGL(k_split_scatter_staged, dim3((unsigned)p.n_groups), dim3(kSplitThreads), 0, st, kp, rec, stg,
-                         (const uint4*)items, (const unsigned*)n_items, fine_cur, (const unsigned*)item_hist);
-    else
-      hipLaunchKernelGGL(k_split_scatter, dim3((unsigned)p.n_groups), dim3(kSplitThreads), 0, st, kp, rec, stg,
-                         (const uint4*)items, (const unsigned*)n_items, fine_cur, (const unsigned*)item_hist);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    uint4* fitems = (uint4*)(ws + w.fine_items);
-    unsigned* n_fitems = (unsigned*)(ws + w.fine_count);
-    PDP_HIP_CHECK(hipMemsetAsync(n_fitems, 0, 4, st));
-    PDP_PROF_BEGIN("k_fine_plan", st);
-    hipLaunchKernelGGL(k_fine_plan, dim3(grid_for(p.n_fine, 1 << 20)), dim3(kBlock), 0, st, kp,
-                       (const unsigned*)fine_total, fitems, n_fitems);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    PDP_HIP_CHECK(hipFuncSetAttribute((const void*)k_fine_reduce, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kFineLds));
-    PDP_PROF_BEGIN("k_fine_reduce", st);
-    hipLaunchKernelGGL(k_fine_reduce, dim3((unsigned)p.fine_items), dim3(kReduceThreads), kFineLds, st, kp, stg,
-                       (const uint4*)fitems, (const unsigned*)n_fitems, acc, err);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-  }
-  return PDP_OK;
+int launch_buckets(int value_kind, bool keep_all, const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid,
+                   const int64_t* pk, const uint8_t* allowed, const void* value,
+                   const pdp_partition_accumulators& acc, char* ws, const Ws& w) {
+  return with_value(value_kind, keep_all, [&](auto vk, auto ka) {
+    return launch_buckets_of<decltype(vk)::value, decltype(ka)::value>(kp, p, st, pid, pk, allowed, value, acc, ws, w);
+  });
 }
+
 
 template <int FMT>
 int launch_scatter(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
@@ -4056,35 +3085,20 @@ int launch_scatter(const KP& kp, const Plan& p, hipStream_t st, const int64_t* p
   using K1 = L1Key<FMT>;
   using K2 = L2Key<FMT>;
   constexpr bool ROWS1 = FMT != PDP_KEYS_PACKED;
-  const size_t lds = sizeof(StageLds<K1, kSmallDest, ROWS1, kL1Items, kL1Threads>);
-  PDP_HIP_CHECK(hipFuncSetAttribute((const void*)k_scatter_l1<FMT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-  PDP_PROF_BEGIN("k_scatter_l1", st);
-  hipLaunchKernelGGL(k_scatter_l1<FMT>, dim3((unsigned)p.n_tiles), dim3(kL1Threads), lds, st, kp, pid, pk,
-                     allowed, super_off, super_base, (K1*)(ws + w.keys1), ROWS1 ? (unsigned*)(ws + w.rows1) : nullptr,
-                     err);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  if (p.super_bits > 0) {
-    const int64_t n_grp = (p.n_tiles + kL2GroupTiles - 1) / kL2GroupTiles;
-    const bool small = ((int64_t)1 << p.super_bits) <= kSmallDest;
-    const void* l2 = small ? (const void*)k_scatter_l2<FMT, kSmallDest> : (const void*)k_scatter_l2<FMT, kMaxDest>;
-    const size_t lds2 =
-        small ? sizeof(StageLds<K2, kSmallDest, true, kL2Items, kL2Threads>)
-              : sizeof(StageLds<K2, kMaxDest, true, kL2Items, kL2Threads>);
-    PDP_HIP_CHECK(hipFuncSetAttribute(l2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    const K1* keys1 = (const K1*)(ws + w.keys1);
-    const unsigned* rows1 = ROWS1 ? (const unsigned*)(ws + w.rows1) : nullptr;
-    K2* keys2 = (K2*)(ws + w.keys2);
-    unsigned* rows2 = (unsigned*)(ws + w.rows2);
-    void* args[] = {(void*)&kp, (void*)&super_base, (void*)&super_off, (void*)&bucket_start, (void*)&gcur,
-                    (void*)&keys1, (void*)&rows1, (void*)&keys2, (void*)&rows2};
-    PDP_PROF_BEGIN("k_scatter_l2", st);
-    PDP_HIP_CHECK(hipLaunchKernel(l2, dim3((unsigned)n_grp, (unsigned)p.n_supers), dim3(kL2Threads), args, lds2, st));
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-  }
-  return PDP_OK;
+  K1* keys1 = (K1*)(ws + w.keys1);
+  unsigned* rows1 = ROWS1 ? (unsigned*)(ws + w.rows1) : nullptr;
+  int rc = launch_big_lds("k_scatter_l1", k_scatter_l1<FMT>, dim3((unsigned)p.n_tiles), dim3(kL1Threads),
+                          sizeof(StageLds<K1, kSmallDest, ROWS1, kL1Items, kL1Threads>), st, kp, pid, pk, allowed,
+                          super_off, super_base, keys1, rows1, err);
+  if (rc != PDP_OK || p.super_bits == 0) return rc;
+  const int64_t n_grp = (p.n_tiles + kL2GroupTiles - 1) / kL2GroupTiles;
+  const bool small = ((int64_t)1 << p.super_bits) <= kSmallDest;
+  const auto l2 = small ? k_scatter_l2<FMT, kSmallDest> : k_scatter_l2<FMT, kMaxDest>;
+  const size_t lds2 = small ? sizeof(StageLds<K2, kSmallDest, true, kL2Items, kL2Threads>)
+                            : sizeof(StageLds<K2, kMaxDest, true, kL2Items, kL2Threads>);
+  return launch_big_lds("k_scatter_l2", l2, dim3((unsigned)n_grp, (unsigned)p.n_supers), dim3(kL2Threads), lds2, st,
+                        kp, super_base, super_off, bucket_start, gcur, keys1, rows1, (K2*)(ws + w.keys2),
+                        (unsigned*)(ws + w.rows2));
 }
 
 // compute units of the current device (cached per device)
@@ -4121,17 +3135,14 @@ int launch_fills(const Fills& f, hipStream_t st) {
   int64_t most = 0;
   for (int j = 0; j < f.k; ++j) most = std::max(most, f.n[j]);
   if (most == 0) return PDP_OK;
-  PDP_PROF_BEGIN("k_fill", st);
-  hipLaunchKernelGGL(k_fill, dim3((unsigned)std::min<int64_t>((most + kBlock - 1) / kBlock, 256)), dim3(kBlock), 0, st, f);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch("k_fill", k_fill, dim3((unsigned)std::min<int64_t>((most + kBlock - 1) / kBlock, 256)), dim3(kBlock),
+                0, st, f);
 }
 
 // tile-local level 1 -> level-2 cursors and bucket starts -> tile-local level 2
 template <int FMT>
-int launch_local(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
-                 const uint8_t* allowed, char* ws, const Ws& w, unsigned* err) {
+int launch_local_fmt(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
+                     const uint8_t* allowed, char* ws, const Ws& w, unsigned* err) {
   using K1 = L1Key<FMT>;
   using K2 = L2Key<FMT>;
   constexpr bool ROWS1 = !kPackedL1<FMT>;
@@ -4147,21 +3158,16 @@ int launch_local(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid
   if constexpr (FMT != PDP_KEYS_WIDE) {
     if (p.sieve) {
       const int th = p.sieve_threads;
-      const size_t lds1 = (size_t)sieve_lds(FMT, th, p.n_buckets, u16, p.band != 0);
-      auto pick = [&](auto th_tag) -> const void* {
+      auto pick = [&](auto th_tag) {
         constexpr int TH = decltype(th_tag)::value;
-        return p.band ? (u16 ? (const void*)k_sieve_l1<FMT, true, true, TH> : (const void*)k_sieve_l1<FMT, false, true, TH>)
-                      : (u16 ? (const void*)k_sieve_l1<FMT, true, false, TH> : (const void*)k_sieve_l1<FMT, false, false, TH>);
+        return p.band ? (u16 ? k_sieve_l1<FMT, true, true, TH> : k_sieve_l1<FMT, false, true, TH>)
+                      : (u16 ? k_sieve_l1<FMT, true, false, TH> : k_sieve_l1<FMT, false, false, TH>);
       };
-      const void* l1 = th == kSieveThreads2 ? pick(std::integral_constant<int, kSieveThreads2>{})
-                                            : pick(std::integral_constant<int, kL1Threads>{});
-      PDP_HIP_CHECK(hipFuncSetAttribute(l1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-      unsigned long long* band = p.band ? (unsigned long long*)(ws + w.band) : nullptr;
-      unsigned* band_cnt = p.band ? (unsigned*)(ws + w.band_cnt) : nullptr;
-      void* args1[] = {(void*)&kp,   (void*)&pid,   (void*)&pk,    (void*)&allowed, (void*)&counts_tm,
-                       (void*)&counts_tm2, (void*)&soff, (void*)&sbase, (void*)&keys1, (void*)&rows1, (void*)&err,
-                       (void*)&band, (void*)&band_cnt, (void*)&tile_over};
-      PDP_PROF_BEGIN("k_sieve_l1", st);
+      const auto l1 = th == kSieveThreads2 ? pick(std::integral_constant<int, kSieveThreads2>{})
+                                           : pick(std::integral_constant<int, kL1Threads>{});
+      const size_t lds1 = (size_t)sieve_lds(FMT, th, p.n_buckets, u16, p.band != 0);
+      int rc = allow_dynamic_lds(l1, lds1);
+      if (rc != PDP_OK) return rc;
       // persistent: as many workgroups as fit at once (one per CU at 1,024
       // threads, two at 512), each looping over its tiles
       const int64_t per_cu = th == kSieveThreads2 ? 2 : 1;
@@ -4173,76 +3179,58 @@ int launch_local(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid
         const long long v = g != nullptr ? std::atoll(g) : 0;
         if (v > 0 && v < grid1) grid1 = v;
       }
-      PDP_HIP_CHECK(hipLaunchKernel(l1, dim3((unsigned)grid1), dim3(th), args1, lds1, st));
-      PDP_PROF_END(st);
-      PDP_HIP_CHECK(hipGetLastError());
+      rc = launch("k_sieve_l1", l1, dim3((unsigned)grid1), dim3(th), lds1, st, kp, pid, pk, allowed, counts_tm,
+                  counts_tm2, soff, sbase, keys1, rows1, err, p.band ? (unsigned long long*)(ws + w.band) : nullptr,
+                  p.band ? (unsigned*)(ws + w.band_cnt) : nullptr, tile_over);
+      if (rc != PDP_OK) return rc;
     }
   }
   if ((kp.clip.flags & PDP_PROBE_LEVEL1) && p.sieve) return PDP_OK;  // placement probe: level 1 only
   if (test_hooks_enabled() && std::getenv("PIPELINEDP_AMD_STOP_AFTER_L1") != nullptr && p.sieve) return PDP_OK;
+  int rc = PDP_OK;
   if (!p.sieve) {
     const size_t lds1 = (l1_stage_bytes(FMT) + 7) / 8 * 8 + (size_t)l1_hist_bytes(p.n_buckets, u16);
-    const void* l1 = u16 ? (const void*)k_scatter_l1_local<FMT, true> : (const void*)k_scatter_l1_local<FMT, false>;
-    PDP_HIP_CHECK(hipFuncSetAttribute(l1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    void* args1[] = {(void*)&kp,         (void*)&pid,  (void*)&pk,    (void*)&allowed, (void*)&counts_tm,
-                     (void*)&counts_tm2, (void*)&soff, (void*)&keys1, (void*)&rows1,   (void*)&err,
-                     (void*)&tile_over};
-    PDP_PROF_BEGIN("k_scatter_l1", st);
     // (one workgroup per tile: a persistent form with the next stage's loads
     // issued early measured the same at C5, 3.04 vs 3.06 ms -- the 2:1
     // read/write mix, not load latency, bounds it; profiles/r04/ab/ab3_l1_local.txt)
-    PDP_HIP_CHECK(hipLaunchKernel(l1, dim3((unsigned)p.n_tiles), dim3(kL1Threads), args1, lds1, st));
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
+    rc = launch_big_lds("k_scatter_l1", u16 ? k_scatter_l1_local<FMT, true> : k_scatter_l1_local<FMT, false>,
+                        dim3((unsigned)p.n_tiles), dim3(kL1Threads), lds1, st, kp, pid, pk, allowed, counts_tm,
+                        counts_tm2, soff, keys1, rows1, err, tile_over);
+    if (rc != PDP_OK) return rc;
     if (kp.clip.flags & PDP_PROBE_LEVEL1) return PDP_OK;  // placement probe: level 1 only
   }
   const int64_t n_bblk8 = (p.n_buckets + 511) / 512;  // k_gscan_sums<true>: eight buckets per lane
   const int64_t n_sc = (p.n_tiles + kScanChunkTiles - 1) / kScanChunkTiles;
   unsigned* csum = (unsigned*)(ws + w.csum);
   unsigned* gcur = (unsigned*)(ws + w.gcur);
-  PDP_PROF_BEGIN("k_gscan_sums", st);
-  hipLaunchKernelGGL(k_gscan_sums<true>, dim3((unsigned)n_bblk8, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
-                     (const unsigned*)counts_tm, (const unsigned*)counts_tm2, (const unsigned*)tile_over, p.n_tiles,
-                     p.n_buckets, kp.cstride, csum, gcur);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_gscan_chunks", st);
-  hipLaunchKernelGGL(k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc, p.n_buckets,
-                     counts);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
+  rc = launch("k_gscan_sums", k_gscan_sums<true>, dim3((unsigned)n_bblk8, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
+              counts_tm, counts_tm2, tile_over, p.n_tiles, p.n_buckets, kp.cstride, csum, gcur);
+  if (rc != PDP_OK) return rc;
+  rc = launch("k_gscan_chunks", k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc,
+              p.n_buckets, counts);
+  if (rc != PDP_OK) return rc;
   // level-2 cursors from the group sums (one pass over counts_tm in all)
-  PDP_PROF_BEGIN("k_gscan_groups", st);
-  hipLaunchKernelGGL(k_gscan_groups, dim3(grid_for(n_sc * p.n_buckets, (int64_t)1 << 30)), dim3(kBlock), 0, st,
-                     (const unsigned*)csum, p.n_tiles, p.n_buckets, gcur);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  const int rc = scan_u32(counts, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);
+  rc = launch("k_gscan_groups", k_gscan_groups, dim3(grid_for(n_sc * p.n_buckets, (int64_t)1 << 30)), dim3(kBlock), 0,
+              st, csum, p.n_tiles, p.n_buckets, gcur);
+  if (rc != PDP_OK) return rc;
+  rc = scan_u32(counts, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);
   if (rc != PDP_OK) return rc;
   const int64_t n_grp = (p.n_tiles + kL2GroupTiles - 1) / kL2GroupTiles;
   const bool small = ((int64_t)1 << p.super_bits) <= kSmallDest;
-  const void* l2 = small ? (const void*)k_scatter_l2_local<FMT, kSmallDest>
-                         : (const void*)k_scatter_l2_local<FMT, kMaxDest>;
+  const auto l2 = small ? k_scatter_l2_local<FMT, kSmallDest> : k_scatter_l2_local<FMT, kMaxDest>;
   const size_t lds2 = small ? sizeof(StageLds<K2, kSmallDest, kL2RowArray<FMT>, l2_items<FMT>(), kL2Threads>)
                             : sizeof(StageLds<K2, kMaxDest, kL2RowArray<FMT>, l2_items<FMT>(), kL2Threads>);
-  PDP_HIP_CHECK(hipFuncSetAttribute(l2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  const uint16_t* soff_c = soff;
-  const unsigned* sbase_c = sbase;
-  const unsigned* counts_c = counts;
-  const unsigned* gcur_c = gcur;
-  const K1* keys1_c = keys1;
-  const unsigned* rows1_c = rows1;
-  K2* keys2 = (K2*)(ws + w.keys2);
-  unsigned* rows2 = (unsigned*)(ws + w.rows2);
-  void* args[] = {(void*)&kp,       (void*)&soff_c,  (void*)&sbase_c, (void*)&counts_c, (void*)&gcur_c,
-                  (void*)&keys1_c, (void*)&rows1_c, (void*)&keys2,   (void*)&rows2};
-  PDP_PROF_BEGIN("k_scatter_l2", st);
   const int64_t n_mgrp = (n_grp + kp.l2_group_mult - 1) / kp.l2_group_mult;  // tile groups per workgroup
   const int64_t n_blk = (n_mgrp + 7) / 8 * 8 * p.n_supers;  // k_scatter_l2_local maps ids to (group, super)
-  PDP_HIP_CHECK(hipLaunchKernel(l2, dim3((unsigned)n_blk), dim3(kL2Threads), args, lds2, st));
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch_big_lds("k_scatter_l2", l2, dim3((unsigned)n_blk), dim3(kL2Threads), lds2, st, kp, soff, sbase, counts,
+                        gcur, keys1, rows1, (K2*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
+}
+
+int launch_local(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
+                 const uint8_t* allowed, char* ws, const Ws& w, unsigned* err) {
+  return with_key_format(p.key_format, [&](auto fmt) {
+    return launch_local_fmt<decltype(fmt)::value>(kp, p, st, pid, pk, allowed, ws, w, err);
+  });
 }
 
 // PDP_DEBUG_CORRUPT_RECORDS (tests only): every level-2 record of bucket 0
@@ -4268,19 +3256,11 @@ __global__ void __launch_bounds__(kBlock) k_debug_corrupt(KP kp, const unsigned*
 }
 
 int launch_debug_corrupt(const KP& kp, const Plan& p, hipStream_t st, char* ws, const Ws& w) {
-  const int rec = rec_of(p.key_format);
-  const unsigned* starts = (const unsigned*)(ws + w.counts);
-  if (rec == kRecCompact)
-    hipLaunchKernelGGL(k_debug_corrupt<kRecCompact>, dim3(64), dim3(kBlock), 0, st, kp, starts,
-                       (uint32_t*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
-  else if (rec == kRecP64)
-    hipLaunchKernelGGL(k_debug_corrupt<kRecP64>, dim3(64), dim3(kBlock), 0, st, kp, starts,
-                       (unsigned long long*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
-  else
-    hipLaunchKernelGGL(k_debug_corrupt<kRecWide>, dim3(64), dim3(kBlock), 0, st, kp, starts,
-                       (unsigned long long*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return with_rec(rec_of(p.key_format), [&](auto rec) {
+    constexpr int REC = decltype(rec)::value;
+    return launch(nullptr, k_debug_corrupt<REC>, dim3(64), dim3(kBlock), 0, st, kp, (const unsigned*)(ws + w.counts),
+                  (RecKey<REC == kRecCompact>*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
+  });
 }
 
 // histogram pass over the privacy ids -> global offsets -> level 1 -> level 2
@@ -4289,90 +3269,45 @@ int launch_offsets(const KP& kp, const Plan& p, hipStream_t st, const int64_t* p
                    const int64_t* partition_key, const uint8_t* pk_allowed, char* ws, const Ws& w, unsigned* err) {
   unsigned* counts = (unsigned*)(ws + w.counts);
   unsigned* counts_tm = (unsigned*)(ws + w.counts_tm);
-  unsigned* chunk_sums = (unsigned*)(ws + w.chunk_sums);
-  const size_t hist_lds = (size_t)p.n_buckets * 4;
-  PDP_HIP_CHECK(hipFuncSetAttribute((const void*)k_part_hist, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)hist_lds));
-  PDP_PROF_BEGIN("k_part_hist", st);
   unsigned* super_tm = (unsigned*)(ws + w.super_tm);
   unsigned* super_off = (unsigned*)(ws + w.super_off);
-  hipLaunchKernelGGL(k_part_hist, dim3((unsigned)p.n_tiles), dim3(kPartThreads), hist_lds, st, kp, privacy_id,
-                     counts_tm, super_tm, err);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_super_scan", st);
-  hipLaunchKernelGGL(k_super_scan, dim3((unsigned)p.n_supers), dim3(kBlock), 0, st, kp, super_tm, super_off);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
+  int rc = launch_big_lds("k_part_hist", k_part_hist, dim3((unsigned)p.n_tiles), dim3(kPartThreads),
+                          (size_t)p.n_buckets * 4, st, kp, privacy_id, counts_tm, super_tm, err);
+  if (rc != PDP_OK) return rc;
+  rc = launch("k_super_scan", k_super_scan, dim3((unsigned)p.n_supers), dim3(kBlock), 0, st, kp, super_tm, super_off);
+  if (rc != PDP_OK) return rc;
   // rows per bucket (and, with two levels, the level-2 cursors at tile-group starts)
   const int64_t n_bblk = (p.n_buckets + 63) / 64;
   const int64_t n_bblk4 = (p.n_buckets + 255) / 256;
   const int64_t n_sc = (p.n_tiles + kScanChunkTiles - 1) / kScanChunkTiles;
   unsigned* csum = (unsigned*)(ws + w.csum);
   unsigned* gcur = (unsigned*)(ws + w.gcur);
-  PDP_PROF_BEGIN("k_gscan_sums", st);
-  hipLaunchKernelGGL(k_gscan_sums<false>, dim3((unsigned)n_bblk4, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
-                     (const unsigned*)counts_tm, (const unsigned*)nullptr, (const unsigned*)nullptr, p.n_tiles,
-                     p.n_buckets, kp.cstride, csum, (unsigned*)nullptr);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_gscan_chunks", st);
-  hipLaunchKernelGGL(k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc, p.n_buckets,
-                     counts);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
+  rc = launch("k_gscan_sums", k_gscan_sums<false>, dim3((unsigned)n_bblk4, (unsigned)n_sc), dim3(64 * kScanWaves), 0,
+              st, counts_tm, nullptr, nullptr, p.n_tiles, p.n_buckets, kp.cstride, csum, nullptr);
+  if (rc != PDP_OK) return rc;
+  rc = launch("k_gscan_chunks", k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc,
+              p.n_buckets, counts);
+  if (rc != PDP_OK) return rc;
   if (p.super_bits > 0) {
-    PDP_PROF_BEGIN("k_gscan_cursors", st);
-    hipLaunchKernelGGL(k_gscan_cursors, dim3((unsigned)n_bblk, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
-                       counts_tm, (const unsigned*)nullptr, p.n_tiles, p.n_buckets, kp.cstride, (const unsigned*)csum,
-                       gcur);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
+    rc = launch("k_gscan_cursors", k_gscan_cursors, dim3((unsigned)n_bblk, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
+                counts_tm, nullptr, p.n_tiles, p.n_buckets, kp.cstride, csum, gcur);
+    if (rc != PDP_OK) return rc;
   }
-  const int rc = scan_u32(counts, p.n_buckets, chunk_sums, st);
+  rc = scan_u32(counts, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);
   if (rc != PDP_OK) return rc;
   unsigned* super_base = (unsigned*)(ws + w.super_base);
-  PDP_PROF_BEGIN("k_super_bases", st);
-  hipLaunchKernelGGL(k_super_bases, dim3(grid_for(p.n_supers + 1)), dim3(kBlock), 0, st, kp, counts, super_base);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  if (p.key_format == PDP_KEYS_COMPACT)
-    return launch_scatter<PDP_KEYS_COMPACT>(kp, p, st, privacy_id, partition_key, pk_allowed, super_off, super_base,
-                                            counts, gcur, ws, w, err);
-  if (p.key_format == PDP_KEYS_PACKED)
-    return launch_scatter<PDP_KEYS_PACKED>(kp, p, st, privacy_id, partition_key, pk_allowed, super_off, super_base,
-                                           counts, gcur, ws, w, err);
-  return launch_scatter<PDP_KEYS_WIDE>(kp, p, st, privacy_id, partition_key, pk_allowed, super_off, super_base,
-                                       counts, gcur, ws, w, err);
+  rc = launch("k_super_bases", k_super_bases, dim3(grid_for(p.n_supers + 1)), dim3(kBlock), 0, st, kp, counts,
+              super_base);
+  if (rc != PDP_OK) return rc;
+  // three formats only: PACKED_WIDE and PACKED64 are planned with tile-local level 1 alone
+  auto scatter = [&](auto fmt) {
+    return launch_scatter<decltype(fmt)::value>(kp, p, st, privacy_id, partition_key, pk_allowed, super_off,
+                                                super_base, counts, gcur, ws, w, err);
+  };
+  if (p.key_format == PDP_KEYS_COMPACT) return scatter(std::integral_constant<int, PDP_KEYS_COMPACT>{});
+  if (p.key_format == PDP_KEYS_PACKED) return scatter(std::integral_constant<int, PDP_KEYS_PACKED>{});
+  return scatter(std::integral_constant<int, PDP_KEYS_WIDE>{});
 }
-
-template <template <int, bool> class F, typename... A>
-int dispatch(int value_kind, bool keep_all, A&&... args) {
-  switch (value_kind) {
-    case PDP_VALUE_NONE:
-      return keep_all ? F<PDP_VALUE_NONE, true>::run(args...) : F<PDP_VALUE_NONE, false>::run(args...);
-    case PDP_VALUE_F64:
-      return keep_all ? F<PDP_VALUE_F64, true>::run(args...) : F<PDP_VALUE_F64, false>::run(args...);
-    default:
-      return keep_all ? F<PDP_VALUE_I64, true>::run(args...) : F<PDP_VALUE_I64, false>::run(args...);
-  }
-}
-
-template <int VK, bool KA>
-struct GlobalRows {
-  template <typename... A>
-  static int run(A&&... a) { return launch_global_rows<VK, KA>(a...); }
-};
-template <int VK, bool KA>
-struct GlobalReduce {
-  template <typename... A>
-  static int run(A&&... a) { return launch_global_reduce<VK, KA>(a...); }
-};
-template <int VK, bool KA>
-struct Buckets {
-  template <typename... A>
-  static int run(A&&... a) { return launch_buckets<VK, KA>(a...); }
-};
 
 int check_ws(const pdp_bound_config* cfg, const void* workspace, uint64_t workspace_bytes, Plan* p, Ws* w) {
   const int rc = validate(cfg);
@@ -4471,13 +3406,10 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
     if (cfg->linf > 0) PDP_HIP_CHECK(hipMemsetAsync(ws + w.rows, 0xFF, slots * (uint64_t)cfg->linf * 8, st));
     else PDP_HIP_CHECK(hipMemsetAsync(ws + w.fsum, 0, w.total - w.fsum, st));
     if (cfg->n_rows == 0) return PDP_OK;
-    PDP_PROF_BEGIN("k_pair_sketch", st);
-    hipLaunchKernelGGL(k_pair_sketch, dim3(grid_for(cfg->n_rows)), dim3(kBlock), 0, st, kp, privacy_id,
-                       partition_key, pk_allowed, (unsigned long long*)(ws + w.sketch), err);
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-    return dispatch<GlobalRows>(cfg->value_kind, cfg->linf == 0, kp, st, privacy_id, partition_key, value,
-                                pk_allowed, ws, w);
+    rc = launch("k_pair_sketch", k_pair_sketch, dim3(grid_for(cfg->n_rows)), dim3(kBlock), 0, st, kp, privacy_id,
+                partition_key, pk_allowed, (unsigned long long*)(ws + w.sketch), err);
+    if (rc != PDP_OK) return rc;
+    return launch_global_rows(cfg, kp, st, privacy_id, partition_key, value, pk_allowed, ws, w);
   }
   // bucketed: histogram -> transpose -> scan -> cursors -> scatter (1 or 2 levels)
   unsigned* counts = (unsigned*)(ws + w.counts);  // rows per bucket -> bucket starts
@@ -4508,20 +3440,8 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
     if (rcf != PDP_OK) return rcf;
   }
   int rc2 = PDP_OK;
-  if (p.l1_local) {
-    if (p.key_format == PDP_KEYS_COMPACT)
-      rc2 = launch_local<PDP_KEYS_COMPACT>(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-    else if (p.key_format == PDP_KEYS_PACKED)
-      rc2 = launch_local<PDP_KEYS_PACKED>(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-    else if (p.key_format == PDP_KEYS_PACKED_WIDE)
-      rc2 = launch_local<PDP_KEYS_PACKED_WIDE>(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-    else if (p.key_format == PDP_KEYS_PACKED64)
-      rc2 = launch_local<PDP_KEYS_PACKED64>(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-    else
-      rc2 = launch_local<PDP_KEYS_WIDE>(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-  } else {
-    rc2 = launch_offsets(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-  }
+  if (p.l1_local) rc2 = launch_local(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
+  else rc2 = launch_offsets(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
   if (rc2 != PDP_OK) return rc2;
   if (cfg->flags & PDP_PROBE_LEVEL1) return PDP_OK;  // placement probe: level 1 only
   // test hook (tools/l1_probe.py): level 1 alone, timed by the profiler;
@@ -4535,8 +3455,8 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
     if (rc2 != PDP_OK) return rc2;
   }
   const pdp_partition_accumulators none{};
-  return dispatch<Buckets>(cfg->value_kind, cfg->linf == 0, kp, p, st, privacy_id, partition_key, pk_allowed, value,
-                           none, ws, w);
+  return launch_buckets(cfg->value_kind, cfg->linf == 0, kp, p, st, privacy_id, partition_key, pk_allowed, value,
+                        none, ws, w);
 }
 
 int pdp_bound_stats_read(const pdp_bound_config* cfg, const void* workspace, uint64_t workspace_bytes,
@@ -4614,7 +3534,7 @@ int pdp_reduce_partitions(const pdp_bound_config* cfg, const void* value, void* 
   if (pairs_mode(cfg)) return pairs_reduce(cfg, value, ws, *acc, st);
   const KP kp = make_kp(cfg, p);
   if (p.algorithm == PDP_ALGO_GLOBAL_SKETCH)
-    return dispatch<GlobalReduce>(cfg->value_kind, cfg->linf == 0, kp, st, value, ws, w, *acc);
+    return launch_global_reduce(cfg, kp, st, value, ws, w, *acc);
   if (cfg->n_rows == 0) return PDP_OK;
   if (p.merge == PDP_MERGE_RANGES) return launch_merge(kp, p, st, ws, w, *acc);
   if (cfg->flags & PDP_DEBUG_CORRUPT_RECORDS) {
@@ -4622,8 +3542,7 @@ int pdp_reduce_partitions(const pdp_bound_config* cfg, const void* value, void* 
     if (rc != PDP_OK) return rc;
   }
   // PDP_MERGE_ATOMIC (never sieved: the key columns are not needed here)
-  return dispatch<Buckets>(cfg->value_kind, cfg->linf == 0, kp, p, st, (const int64_t*)nullptr,
-                           (const int64_t*)nullptr, (const uint8_t*)nullptr, value, *acc, ws, w);
+  return launch_buckets(cfg->value_kind, cfg->linf == 0, kp, p, st, nullptr, nullptr, nullptr, value, *acc, ws, w);
 }
 
 }  // extern "C"

@@ -1,0 +1,186 @@
+// pdp_bound_plan.h -- what the bounding sources (pdp_bound*.hip) share on the
+// host: the constants of the plan and the kernels, Plan / Ws / KP /
+// PairRecords, and the entry points of the passes that have their own file.
+#pragma once
+
+#include "pdp_internal.h"
+
+namespace pdp {
+
+constexpr int kPartThreads = 512;
+// rows per thread and LDS stage of the level-1 scatter / level-2 window
+constexpr int kL1Threads = 1024;
+constexpr int kL1Items = 8;
+constexpr int kL1Rows = kL1Threads * kL1Items;  // rows per level-1 LDS stage
+constexpr int kL2Items = 16;
+// level 2: two 8-wave workgroups per CU need <= 128 VGPRs (MI355X_MICROARCH.md
+// register table): the kernel takes 121-123 with 16 records per thread;
+// loading a stage ahead (157 VGPRs, one workgroup per CU) cost 1 ms at C3
+constexpr int kL2Threads = 512;
+constexpr int kL2Rows = kL2Threads * kL2Items;  // records per level-2 LDS stage
+// tiles per level-2 workgroup (k_scatter_l2, k_gscan_cursors)
+constexpr int kL2GroupTiles = 16;
+constexpr int kScanWaves = 16;
+constexpr int kScanTiles = 16;  // tiles per wave in the level-2 cursor scans; multiple of kL2GroupTiles
+constexpr int kScanChunkTiles = kScanWaves * kScanTiles;
+static_assert(kScanTiles % kL2GroupTiles == 0, "group starts must fall inside a wave's tiles");
+constexpr int kTileRowBits = 16;
+constexpr int64_t kTileRows = (int64_t)1 << kTileRowBits;
+constexpr int kStagesPerTile = (int)(kTileRows / kL1Rows);  // level-1 blocks per tile
+constexpr int kL2Runs = kL2GroupTiles * kStagesPerTile;  // level-1 runs per level-2 workgroup
+constexpr int kUnroll = 8;
+constexpr int kBucketThreads = 1024;
+constexpr int64_t kLdsBudget = 124 * 1024;  // per-pid state; + range scratch + wave queues <= 160 KiB
+// 512-thread bucket workgroups: per-pid state <= 56 KiB, so that with the
+// range scratch (<= 4 KiB at 512 ranges), 8 wave queues (12 KiB) and the pid
+// hashes two workgroups fit one CU's 160 KiB
+constexpr int64_t kLdsBudget2 = 56 * 1024;
+constexpr int kMinRandomBits = 24;
+constexpr int64_t kMaxBuckets = 36 * 1024;  // u32 histogram in 144 KiB of LDS
+constexpr int kMaxSupers = 128;   // destinations of a level-1 scatter
+constexpr int64_t kSingleLevelMax = 64;      // buckets partitioned by one level
+constexpr int kRangeBits = 11;                // partitions per merge range = 2048
+constexpr int kRangeParts = 1 << kRangeBits;
+constexpr int kMaxRanges = kBucketThreads;    // per-bucket range histogram <= one block scan
+// More partitions than kMaxRanges ranges of 2^kRangeBits: the bucket kernel
+// groups kept pairs by coarse ranges of 2^range_bits partitions (<= kCoarseRanges
+// of them), k_split_* re-sort each coarse range's records into its
+// 2^kRangeBits-partition ranges, k_fine_reduce sums them (two-level merge)
+constexpr int kCoarseRanges = 256;
+constexpr int kRangeThreads = 1024;  // k_range_plan workgroups
+// range-reduce work item: the records of one partition range from a run of
+// consecutive buckets, cut at bucket boundaries every kRangeChunk records
+// (k_range_plan), so a Zipf-hot range spreads over many workgroups and a cold
+// one is a single item
+constexpr int64_t kRangeChunk = 8192;
+constexpr unsigned kRangeDirect = 256;        // records below which a workgroup adds them directly
+// k_range_reduce / k_fine_reduce workgroups: 512 threads (two per CU by their
+// 68 KB of LDS: 16 waves, not 8): C3 k_range_reduce 0.275 -> 0.195 ms, C4
+// k_fine_reduce 0.574 -> 0.540 (1,024: 0.212 / 0.537; profiles/r05/ab/ab12_merge_threads.txt)
+constexpr int kReduceThreads = 512;
+constexpr int kSplitThreads = 512;  // k_split_count / k_split_scatter workgroups
+constexpr size_t kRangeLds = kRangeParts * (3 * 8 + 2 * 4) + kReduceThreads * (8 + 4) + (kReduceThreads / 64 + 1) * 4;
+constexpr int kQueueCap = 128;                // per-wave candidate queue (bucket kernel)
+constexpr int kScanItems = 16;
+constexpr int kScanChunk = kBlock * kScanItems;
+
+struct Plan {
+  int algorithm;   // PDP_ALGO_*
+  int pk_bits;
+  int bucket_bits;
+  int super_bits;
+  int rand_shift;
+  int64_t n_buckets;
+  int64_t n_supers;
+  int64_t n_tiles;
+  int64_t lds_bytes;
+  int merge;            // PDP_MERGE_* (bucketed)
+  int n_ranges;         // PDP_MERGE_RANGES: ceil(P / 2^range_bits)
+  int range_bits;       // partitions per merge range of the bucket kernel (kRangeBits, or coarse)
+  int two_level;        // range_bits > kRangeBits: coarse ranges, then k_split_* / k_fine_*
+  int64_t n_fine;       // two-level: ceil(P / 2^kRangeBits)
+  int64_t fine_items;   // two-level: upper bound on the k_fine_reduce work items
+  int64_t range_group;  // records per range-reduce work item (kRangeChunk)
+  int64_t n_groups;     // upper bound on the range-reduce work items (+ one sentinel per range)
+  int key_format;       // PDP_KEYS_WIDE / PDP_KEYS_COMPACT (bucketed)
+  int l1_local;         // tile-local level 1 (k_scatter_l1_local / k_scatter_l2_local), no histogram pass
+  int64_t n_stages;     // level-1 stages of kL1Rows rows
+  int sieve;            // threshold sieve: t = sieve / 2^16 (0 = off); k_sieve_l1 instead of k_scatter_l1_local
+  int band;             // side band: t2 = band / 2^16 (0 = off; else 2 * sieve, <= 1/2)
+  int64_t n_slots1;     // level-1 blocks (stages, or sieve flush slots: n_tiles << slot_bits)
+  int64_t buckets_out;  // buckets of pair records: n_buckets, x2 with the sieve (fix-up after), x3 with the band
+  int l2_mult;          // tile groups per level-2 workgroup (1 without the sieve)
+  int sieve_threads;    // k_sieve_l1 workgroup: 1,024 or 512 threads (SieveShape)
+  int bucket_threads;   // k_bucket_bound workgroup: 1,024 or 512 threads (half-size buckets)
+  int slot_bits;        // level-1 blocks per tile = 2^slot_bits (kStagesPerTile, or SieveShape::kSlots)
+  int hist_u16;         // tile-local level 1 counts buckets in u16 halves (counts_tm / counts_tm2)
+};
+
+struct Ws {
+  // common
+  uint64_t err;
+  // global path
+  uint64_t sketch, cnt, rows, fsum, nsum, nsum2;
+  // bucketed path
+  uint64_t counts_tm, counts, chunk_sums, super_base, super_tm, super_off, keys1, rows1, keys2, rows2;
+  uint64_t csum, gcur;  // level-2 cursor scans: per tile chunk, per tile group (x n_buckets)
+  uint64_t cand_key, cand_idx;  // bucket kernel: B1's candidate list (record-local key, row)
+  uint64_t soff;                // tile-local level 1: per stage, super-bucket run starts (u16)
+  uint64_t counts_tm2;          // tile-local level 1, u16 counts: second half-tile bucket counts
+  // threshold sieve: flush-block starts (u32 per slot), unresolved privacy
+  // ids (bitmap + list), {unresolved count, fix-up rows}, fix-up rows per
+  // bucket (-> starts) and their write cursors; the fix-up row list itself
+  // reuses keys1 (dead after level 2), its bucket-ordered records keys2/rows2
+  uint64_t sbase, unres_bits, unres_list, sctl, fix_cnt, fix_cur;
+  // the fix-up's (id << 32 | row) list: the level-1 region (keys1, and rows1
+  // right after it for COMPACT records), dead after level 2; fix_cap entries
+  // (>= n_rows: every list holds distinct rows)
+  uint64_t fix_rec, fix_cap;
+  // side band: per-tile (pid << 32 | row) lists and their lengths; the ids
+  // still unresolved after the band fix-up (bitmap, list, {count, rows}) and
+  // their rescan's per-bucket counts / cursors
+  uint64_t band, band_cnt, unres2_bits, unres2_list, sctl2, fix_cnt2, fix_cur2;
+  uint64_t fix_blist;  // fix-up bucket launches: {count, buckets holding fix-up rows...}
+  uint64_t tile_over;  // tile-local level 1: per tile, the bucket holding all 65,536 of its rows (else ~0)
+  // bucketed PDP_MERGE_RANGES: pair records per bucket block, grouped by range
+  uint64_t runs, rec_key, rec_f0, rec_f1, rec_f2;
+  uint64_t rr_items, rr_count;  // range-reduce work items (uint4) and their count
+  // two-level merge: fine-range totals / starts (+ scan scratch), write cursors,
+  // the records re-sorted by fine range, fine work items and their count
+  uint64_t fine_total, fine_chunks, fine_cur, stg_key, stg_f0, stg_f1, stg_f2, fine_items, fine_count;
+  uint64_t item_hist;  // two-level: per coarse work item, its records per fine range (k_split_count)
+  uint64_t total;
+};
+
+struct KP {  // kernel parameters
+  int64_t n, U, P;
+  int l0, linf;
+  int pk_bits, bucket_bits, super_bits, rand_shift;
+  int64_t n_buckets, n_supers, n_tiles;
+  int n_ranges;
+  int range_bits;
+  int64_t n_fine_ranges;  // two-level merge: ceil(P / 2^kRangeBits)
+  int keys_vec;  // privacy_id / partition_key columns are 16-byte aligned
+  uint64_t pk_mask, seed, row_seed;
+  int64_t row_offset;
+  int64_t cstride;  // row stride of counts_tm / counts_tm2 in buckets: n_buckets rounded up to 8
+  ClipParams clip;
+  int64_t n_slots1;     // level-1 blocks read by level 2 (Plan.n_slots1)
+  int l2_group_mult;    // tile groups per level-2 workgroup
+  uint32_t sieve_t32;   // threshold sieve: candidate rows have pair_hash < sieve_t32 (0 = off)
+  int sieve_mark;       // bucket kernel: mark privacy ids with < l0 candidate pairs unresolved
+  uint32_t band_t32;    // side band: level 1 lists rows with sieve_t32 <= pair_hash < band_t32 (0 = off)
+  int sieve_emit;       // bucket kernel (main launch, band on): unresolved ids' candidate rows -> fix_rec
+  int slot_bits;        // level-1 blocks per tile = 2^slot_bits (Plan.slot_bits)
+  int64_t fix_cap;      // sieve: entries the fix-up row list (fix_rec, Ws.fix_rec) holds
+  int row_shift;        // PACKED64 level-2 records: the row's first bit (pk_bits + bucket_bits)
+};
+
+struct PairRecords {  // PDP_MERGE_RANGES output of the bucket kernel
+  unsigned* runs;                // [n_ranges + 1][run_stride] run starts within the bucket block (range-major)
+  int64_t run_stride;            // buckets_out: one column per output bucket
+  unsigned long long* key;       // (partition << 32) | count
+  double* f0;                    // sum (int64 bits with PDP_SUM_INT)
+  double* f1;                    // normalized sum
+  double* f2;                    // normalized sum of squares
+};
+
+inline PairRecords pair_records(char* ws, const Ws& w, const Plan& p) {
+  PairRecords rec{};
+  if (w.runs) {
+    rec.runs = (unsigned*)(ws + w.runs);
+    rec.run_stride = p.buckets_out;
+    rec.key = (unsigned long long*)(ws + w.rec_key);
+    rec.f0 = w.rec_f0 ? (double*)(ws + w.rec_f0) : nullptr;
+    rec.f1 = w.rec_f1 ? (double*)(ws + w.rec_f1) : nullptr;
+    rec.f2 = w.rec_f2 ? (double*)(ws + w.rec_f2) : nullptr;
+  }
+  return rec;
+}
+
+// pdp_bound_merge.hip -- PDP_MERGE_RANGES: the pair records of every bucket
+// (p.buckets_out of them) summed per partition
+int launch_merge(const KP& kp0, const Plan& p, hipStream_t st, char* ws, const Ws& w,
+                 const pdp_partition_accumulators& acc);
+
+}  // namespace pdp

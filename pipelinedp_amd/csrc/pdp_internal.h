@@ -65,12 +65,6 @@ template <typename T>
 __device__ __forceinline__ T ld_nt(const T* p) {
   return __builtin_nontemporal_load(p);
 }
-// a load that is non-temporal when NT is set (a compile-time choice per site)
-template <bool NT, typename T>
-__device__ __forceinline__ T ld_maybe_nt(const T* p) {
-  if constexpr (NT) return ld_nt(p);
-  else return *p;
-}
 
 inline int bits_for(int64_t n) {  // smallest b >= 1 with 2^b >= n
   int b = 1;
@@ -542,3 +536,39 @@ void profiler_end(hipStream_t stream);
   do { if (::pdp::profiler_enabled()) ::pdp::profiler_begin(name, stream); } while (0)
 #define PDP_PROF_END(stream) \
   do { if (::pdp::profiler_enabled()) ::pdp::profiler_end(stream); } while (0)
+
+// ------------------------------------------------------- kernel launches --
+namespace pdp {
+template <typename T>
+struct Arg {  // a launch argument converts to the kernel's parameter type, which is never deduced from it
+  using type = T;
+};
+
+// Lets `kern` take `bytes` of dynamic LDS (above the 64 KiB default).
+template <typename... KArgs>
+int allow_dynamic_lds(void (*kern)(KArgs...), size_t bytes) {
+  PDP_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return PDP_OK;
+}
+
+// One kernel launch, bracketed for the profiler under `name` (NULL: not
+// timed) and checked.  The arguments are checked against the kernel's
+// signature at compile time, also where `kern` was chosen at run time.
+template <typename... KArgs>
+int launch(const char* name, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+           typename Arg<KArgs>::type... args) {
+  void* argv[] = {(void*)&args...};
+  if (name != nullptr) PDP_PROF_BEGIN(name, st);
+  (void)hipLaunchKernel((const void*)kern, grid, block, argv, lds, st);  // an error stays for hipGetLastError
+  if (name != nullptr) PDP_PROF_END(st);
+  PDP_HIP_CHECK(hipGetLastError());
+  return PDP_OK;
+}
+// The same after allow_dynamic_lds(kern, lds).
+template <typename... KArgs>
+int launch_big_lds(const char* name, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                   typename Arg<KArgs>::type... args) {
+  const int rc = allow_dynamic_lds(kern, lds);
+  return rc != PDP_OK ? rc : launch(name, kern, grid, block, lds, st, args...);
+}
+}  // namespace pdp
