@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 16
+#define PDP_ABI_VERSION 17
 
 /* error codes */
 #define PDP_OK 0
@@ -159,7 +159,8 @@ typedef struct pdp_bound_plan_info {
   int32_t sieve_threads; /* resolved sieve level-1 workgroup size (0 without the sieve) */
   int32_t bucket_threads; /* resolved bucket-kernel workgroup size (BUCKETED) */
   int32_t hist_u16;    /* tile-local level 1 keeps its per-tile bucket counts as u16 halves */
-  int32_t reserved;
+  int32_t fix_ids;     /* sieve fix-up: 1 = one wave per unresolved privacy id (l0 * (1 + linf) <= 32,
+                          linf > 0), 0 = fix-up bucket launches */
 } pdp_bound_plan_info;
 
 /* Resolves the execution plan for `cfg` (no device work). */

@@ -314,7 +314,14 @@ Plan make_plan(const pdp_bound_config* c) {
   if (!p.sieve) p.slot_bits = 3;
   static_assert(kStagesPerTile == 8, "non-sieve level-1 stages per tile = 2^3");
   p.n_slots1 = p.sieve ? p.n_tiles << p.slot_bits : p.n_stages;
-  p.buckets_out = p.sieve ? (p.band ? 3 : 2) * p.n_buckets : p.n_buckets;
+  // the fix-up per privacy id where a wave's sketches (l0 pair entries, l0 *
+  // linf row entries) fit its LDS slice; keep-all-rows plans (per-pair sums,
+  // not row sketches) and larger bounds keep the fix-up bucket launches
+  p.fix_ids = p.sieve && c->linf > 0 && (int64_t)c->l0 * (1 + (int64_t)c->linf) <= kFixIdsEntries;
+  p.pair_slots = (int64_t)c->l0 << p.bucket_bits;
+  // record segments of the range merge: the main launch's, and one per
+  // fix-up bucket launch (the per-id fix-up lists its pairs flat, after them)
+  p.buckets_out = p.sieve && !p.fix_ids ? (p.band ? 3 : 2) * p.n_buckets : p.n_buckets;
   p.l2_mult = 1;
   if (p.sieve) {
     // expected records of one (group of kL2GroupTiles tiles, super-bucket)
@@ -410,7 +417,16 @@ Ws layout(const pdp_bound_config* c, const Plan& p) {
       w.sctl = off; off = align256(off + 16);
       w.fix_cnt = off; off = align256(off + ((uint64_t)p.n_buckets + 1) * 4);
       w.fix_cur = off; off = align256(off + (uint64_t)p.n_buckets * 4);
-      w.fix_blist = off; off = align256(off + ((uint64_t)p.n_buckets + 1) * 4);
+      // listed buckets; per-id fix-up: {bucket, begin, end, id} of every id
+      // over the row cap (their rows are distinct entries of the fix-up list)
+      const uint64_t n_blist = p.fix_ids ? 4 * (w.fix_cap / kFixIdsRowCap + 1) : (uint64_t)p.n_buckets;
+      w.fix_blist = off; off = align256(off + (n_blist + 1) * 4);
+      if (p.fix_ids) {
+        w.id_pos = off; off = align256(off + ids * 4);
+        w.id_seg = off; off = align256(off + ids * 8);
+        if (p.band) { w.id_seg2 = off; off = align256(off + ids * 8); }
+        w.fix_ctl = off; off = align256(off + 16);
+      }
       if (p.band) {  // the band lists; the second fix-up's unresolved ids and counts
         w.band = off; off = align256(off + (uint64_t)p.n_tiles * kBandTileStride * 8);
         w.band_cnt = off; off = align256(off + (uint64_t)p.n_tiles * 4);
@@ -432,7 +448,7 @@ Ws layout(const pdp_bound_config* c, const Plan& p) {
     w.cand_key = off; off = align256(off + n * kb2);
     w.cand_idx = off; off = align256(off + n * 4);
     if (p.merge == PDP_MERGE_RANGES) {
-      const uint64_t recs = (uint64_t)p.buckets_out * ((uint64_t)c->l0 << p.bucket_bits);
+      const uint64_t recs = (uint64_t)(p.buckets_out + (p.fix_ids ? p.n_buckets : 0)) * ((uint64_t)c->l0 << p.bucket_bits);
       w.runs = off; off = align256(off + (uint64_t)p.buckets_out * (p.n_ranges + 1) * 4);
       w.rec_key = off; off = align256(off + recs * 8);
       if (c->flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION)) { w.rec_f0 = off; off = align256(off + recs * 8); }
@@ -532,6 +548,7 @@ KP make_kp(const pdp_bound_config* c, const Plan& p) {
   k.slot_bits = p.slot_bits;
   k.fix_cap = 0;  // set from the layout (Ws.fix_cap) where the fix-up runs
   k.row_shift = p.pk_bits + p.bucket_bits;
+  k.fix_ids = 0;
   k.pk_mask = (1ULL << p.pk_bits) - 1;
   k.seed = c->seed;
   k.row_seed = derive_row_seed(c->seed);
@@ -2244,7 +2261,10 @@ __device__ __forceinline__ int64_t xcd_major(int64_t id, int64_t G) {
   } while (0)
 #endif
 
-template <int VALUE_KIND, bool KEEP_ALL_ROWS, bool RANGES, int REC>
+// FLAT: the per-id fix-up's listed launch (ids over its row cap): blist holds
+// {bucket, begin, end, id}, only that id is marked, and the kept pairs go to
+// the flat list instead of the bucket's record block and runs
+template <int VALUE_KIND, bool KEEP_ALL_ROWS, bool RANGES, int REC, bool FLAT = false>
 __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const RecKey<REC == kRecCompact>* __restrict__ keys,
                                                                  const unsigned* __restrict__ rowidx,
                                                                  const unsigned* __restrict__ offsets,
@@ -2257,13 +2277,17 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
                                                                  unsigned* __restrict__ sctl, unsigned* __restrict__ err,
                                                                  unsigned long long* __restrict__ fix_rec,
                                                                  const unsigned* __restrict__ unres_prev,
-                                                                 const unsigned* __restrict__ blist) {
+                                                                 const unsigned* __restrict__ blist,
+                                                                 unsigned* __restrict__ id_pos,
+                                                                 unsigned* __restrict__ id_seg) {
   constexpr bool COMPACT = REC == kRecCompact;
   extern __shared__ unsigned long long smem[];
   __shared__ unsigned ccount;
   const int64_t S = (int64_t)1 << kp.bucket_bits;
   const int l0 = kp.l0;
-  auto body = [&](const int64_t b) {
+  // b: the bucket; [begin, end): its records; only_id >= 0 (per-id fix-up,
+  // an id over the row cap): the records are that one id's, and only it is marked
+  auto body = [&](const int64_t b, const int64_t begin, const int64_t end, const int64_t only_id) {
 #ifdef PDP_PHASE_CLOCK
   unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};
   if (threadIdx.x == 0) ph[0] = wall_clock64();
@@ -2274,9 +2298,21 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
   // bitmap (a wave covers 64 ids = one u64 word; the bucket's ids are whole
   // words) and list it.  unres_prev (the band's fix-up launch): only ids the
   // main launch left unresolved can be.
+  // per-id fix-up (id_pos != NULL): a listed id's list position goes to
+  // id_pos[id] and its fix-up row count (id_seg, odd words) starts at 0
   auto mark = [&](bool sketch) {
     const int lane = threadIdx.x & 63;
     const int64_t id0 = b << kp.bucket_bits;
+    if constexpr (FLAT) {  // the bitmap was zeroed, other ids' bits are k_fix_ids'
+      if (threadIdx.x == 0 && smem[(int64_t)(l0 - 1) * S + (only_id - id0)] == kEmpty) {
+        atomicOr(unres_bits + (only_id >> 5), 1u << (only_id & 31));
+        const unsigned at = atomicAdd(sctl, 1u);
+        unres_list[at] = (unsigned)only_id;
+        id_pos[only_id] = at;
+        id_seg[2 * (int64_t)at + 1] = 0;
+      }
+      return;
+    }
     for (int64_t p0 = (int64_t)(threadIdx.x >> 6) * 64; p0 < S; p0 += blockDim.x) {
       const int64_t id = id0 + p0 + lane;
       bool un = id < kp.U;
@@ -2288,7 +2324,14 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(sctl, (unsigned)__popcll(m));
         base = __shfl(base, 0, 64);
-        if (un) unres_list[base + __popcll(m & ((1ULL << lane) - 1))] = (unsigned)id;
+        if (un) {
+          const unsigned at = base + __popcll(m & ((1ULL << lane) - 1));
+          unres_list[at] = (unsigned)id;
+          if (id_pos != nullptr) {
+            id_pos[id] = at;
+            id_seg[2 * (int64_t)at + 1] = 0;
+          }
+        }
       }
     }
   };
@@ -2297,7 +2340,7 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
   // band's fix-up launch after marking its previously unresolved ids (none
   // of their pairs is below t2); the main launch's empty buckets still mark
   // their privacy ids unresolved
-  if ((!kp.sieve_mark || unres_prev != nullptr) && offsets[b] == offsets[b + 1]) {  // block-uniform
+  if ((!kp.sieve_mark || unres_prev != nullptr) && begin == end) {  // block-uniform
     if (RANGES) {
       for (int t = threadIdx.x; t <= kp.n_ranges; t += blockDim.x) rec.runs[t * rec.run_stride + b] = 0;
     }
@@ -2340,8 +2383,6 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
     for (int64_t t = threadIdx.x; t < 3 * n_slots; t += blockDim.x) tot[t] = 0.0;
   }
   __syncthreads();
-  const int64_t begin = offsets[b];
-  const int64_t end = offsets[b + 1];  // offsets has n_buckets + 1 entries
   const uint64_t bmask = (uint64_t)S - 1;
   // PACKED64 records (row | local pid | partition; all ones dead) and their
   // candidate-list form (local pid | partition)
@@ -2496,7 +2537,7 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
   }
   PDP_PHASE(4);
   const void* const b3_value = B25 ? nullptr : value;
-  if (RANGES) {
+  if (RANGES && !FLAT) {
     // B3a: kept pairs per partition range -> this bucket's run starts
     for (int64_t slot = threadIdx.x; slot < n_slots; slot += blockDim.x) {
       const uint64_t x = sk[slot];
@@ -2564,7 +2605,14 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
       ps = PairSums{(long long)c, 0, 0.0, 0.0, 0.0};
     }
     if (RANGES) {
-      const int64_t i = b * n_slots + atomicAdd(rcur + (p >> kp.range_bits), 1u);
+      // (per-id fix-up: the flat list of the fix-up's pairs, no runs)
+      int64_t i;
+      if constexpr (FLAT) {
+        i = rec.flat_base + (int64_t)atomicAdd(rec.flat_n, 1u);
+        if (i >= rec.flat_base + rec.flat_cap) continue;  // cannot happen: <= l0 pairs per id
+      } else {
+        i = b * n_slots + atomicAdd(rcur + (p >> kp.range_bits), 1u);
+      }
       rec.key[i] = ((unsigned long long)p << 32) | (unsigned long long)(uint32_t)ps.count;
       if (flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION))
         rec.f0[i] = (flags & PDP_SUM_INT) ? __longlong_as_double(ps.isum) : ps.fsum;
@@ -2582,19 +2630,30 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
            ph[5] - ph[4]);
 #endif
   };
-  if (blist == nullptr) {
+  if constexpr (FLAT) {
+    // the per-id fix-up's ids over the row cap (k_fix_ids listed them): each
+    // entry is one id's rows, a slice of the id-ordered fix-up records
+    const unsigned nb = blist[0];
+    for (unsigned i = blockIdx.x; i < nb; i += gridDim.x) {
+      const unsigned* e = blist + 1 + 4 * (int64_t)i;
+      body((int64_t)e[0], (int64_t)e[1], (int64_t)e[2], (int64_t)e[3]);
+      __syncthreads();
+    }
+  } else if (blist == nullptr) {
     // XCD-aware bucket order: workgroups are dispatched round-robin over the
     // 8 XCDs (blockIdx % 8), so XCD x takes one contiguous block of buckets
     // and its writes to the range-major run table (and the records) share L2
     // lines
-    body(xcd_major(blockIdx.x, gridDim.x));
+    const int64_t b = xcd_major(blockIdx.x, gridDim.x);
+    body(b, offsets[b], offsets[b + 1], -1);  // offsets has n_buckets + 1 entries
   } else {
     // a fix-up launch over the buckets that hold fix-up rows only (blist[0]
     // of them, listed from blist[1]; k_fix_buckets did the empty ones'
     // work): a persistent loop, one bucket at a time
     const unsigned nb = blist[0];
     for (unsigned i = blockIdx.x; i < nb; i += gridDim.x) {
-      body((int64_t)blist[1 + i]);
+      const int64_t b = (int64_t)blist[1 + i];
+      body(b, offsets[b], offsets[b + 1], -1);
       __syncthreads();  // the LDS state is the next bucket's
     }
   }
@@ -2917,6 +2976,250 @@ __global__ void __launch_bounds__(kBlock) k_fix_buckets(KP kp, const unsigned* _
   }
 }
 
+// ----------------------------------------------------- per-id fix-up --
+// Plan.fix_ids: the fix-up list grouped by privacy id instead of by bucket,
+// and one wave per unresolved id (k_fix_ids) instead of a bucket launch over
+// every bucket.  An unresolved id is known by its position in the unresolved
+// list (id_pos[id], written where the id is listed); seg[2 * pos] and
+// seg[2 * pos + 1] are the start and the end of the id's rows in the
+// id-ordered records (the end counts the rows first, then is the scatter's
+// cursor).  Four launches per round: k_fix_id_count, k_fix_id_alloc,
+// k_fix_id_scatter, k_fix_ids (+ a listed bucket launch for ids over the row
+// cap, else empty).  (The scan folded into the count's last finishing block
+// measured 0.03 ms per launch for its device-scope fences, against 0.007 ms
+// for the launch of its own: profiles/r07.)
+
+// Step 1: k_fix_filter's exact test, the rows counted per id.
+constexpr int kFixScanItems = 8;
+__global__ void __launch_bounds__(kBlock) k_fix_id_count(KP kp, const unsigned* __restrict__ unres_bits,
+                                                         const unsigned* __restrict__ sctl,
+                                                         unsigned long long* __restrict__ fix_rec,
+                                                         const unsigned* __restrict__ id_pos, unsigned* seg,
+                                                         unsigned* err, unsigned* __restrict__ blist) {
+  const int64_t listed = sctl[1];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (listed > kp.fix_cap) atomicOr(err, 2u);  // see k_fix_filter
+    blist[0] = 0;  // k_fix_ids' count of ids over the row cap
+  }
+  const int64_t total = listed < kp.fix_cap ? listed : kp.fix_cap;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t u = fix_rec[i] >> 32;
+    if ((unres_bits[u >> 5] >> (u & 31)) & 1u) atomicAdd(seg + 2 * (int64_t)id_pos[u] + 1, 1u);
+    else fix_rec[i] = ~0ULL;
+  }
+}
+
+// Step 1b: the counts -> starts, one workgroup: an exclusive scan over the
+// unresolved list, eight ids per thread and trip (a few thousand ids at C3)
+__global__ void __launch_bounds__(kBlock) k_fix_id_alloc(const unsigned* __restrict__ sctl, unsigned* __restrict__ seg) {
+  __shared__ unsigned wsum[kBlock / 64 + 1];
+  const int64_t n_ids = sctl[0];
+  unsigned carry = 0;
+  for (int64_t j0 = 0; j0 < n_ids; j0 += (int64_t)kBlock * kFixScanItems) {  // block-uniform trips
+    const int64_t j = j0 + (int64_t)threadIdx.x * kFixScanItems;
+    unsigned c[kFixScanItems], sum = 0;
+#pragma unroll
+    for (int k = 0; k < kFixScanItems; ++k) {
+      c[k] = j + k < n_ids ? seg[2 * (j + k) + 1] : 0u;
+      sum += c[k];
+    }
+    unsigned t;
+    unsigned at = carry + block_excl_scan(sum, wsum, &t);
+#pragma unroll
+    for (int k = 0; k < kFixScanItems; ++k) {
+      if (j + k < n_ids) {
+        seg[2 * (j + k)] = at;
+        seg[2 * (j + k) + 1] = at;
+      }
+      at += c[k];
+    }
+    carry += t;
+    __syncthreads();  // wsum is the next trip's
+  }
+}
+
+// Step 2: k_fix_scatter into id order (the same records: bucket-local pid |
+// partition, dead bit, row), a slot per row from the id's cursor.
+template <int REC>
+__global__ void __launch_bounds__(kBlock) k_fix_id_scatter(KP kp, const int64_t* __restrict__ pk,
+                                                           const uint8_t* __restrict__ allowed,
+                                                           const unsigned long long* __restrict__ fix_rec,
+                                                           const unsigned* __restrict__ sctl,
+                                                           const unsigned* __restrict__ id_pos,
+                                                           unsigned* __restrict__ seg,
+                                                           RecKey<REC == kRecCompact>* __restrict__ keys,
+                                                           unsigned* __restrict__ rows) {
+  const int64_t total = (int64_t)sctl[1] < kp.fix_cap ? (int64_t)sctl[1] : kp.fix_cap;
+  const uint64_t lmask = ((uint64_t)1 << kp.bucket_bits) - 1;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t e = fix_rec[i];
+    if (e == ~0ULL) continue;  // a Bloom false positive (k_fix_id_count)
+    const uint64_t u = e >> 32;
+    const uint32_t r = (uint32_t)e;
+    const int64_t k = pk[r];
+    const bool dead = k < 0 || k >= kp.P || (allowed != nullptr && allowed[k] == 0);
+    const uint64_t lpk = (u & lmask) << kp.pk_bits;
+    const unsigned pos = atomicAdd(seg + 2 * (int64_t)id_pos[u] + 1, 1u);
+    if constexpr (REC == kRecCompact)
+      keys[pos] = (uint32_t)(dead ? (0x80000000ull | lpk) : (lpk | (uint64_t)k));
+    else if constexpr (REC == kRecWide)
+      keys[pos] = dead ? ((1ull << 63) | lpk) : (lpk | (uint64_t)k);
+    else  // PACKED64: the row in the key, all ones if dead
+      keys[pos] = dead ? ~0ull : (((uint64_t)r << kp.row_shift) | lpk | (uint64_t)k);
+    if constexpr (REC != kRecP64) rows[pos] = r;
+  }
+}
+
+// where k_fix_ids lists the ids still short of l0 pairs (the band's round)
+struct IdMarks {
+  unsigned* bits;  // zeroed bitmap
+  unsigned* list;
+  unsigned* sctl;
+  unsigned* seg;   // their row counts start at 0
+};
+
+// Step 3: one wave per unresolved id (a persistent grid over the list).  The
+// wave streams the id's records 64 at a time, twice, with the bucket
+// kernel's steps on a sketch of its own in LDS: B1 the bottom-l0 distinct
+// pair keys (the same keys: pid hash, bucket-local pid, partition); with
+// kp.sieve_mark an id whose sketch is not full is listed in `mk` and emits
+// nothing (the rescan's round finishes it); B2 the rows of kept pairs
+// counted and their bottom-linf row keys; the kept rows' values gathered
+// together (B2.5); B3 one pair record per kept pair, appended to the flat
+// list that the reduce kernels add to the partitions.  An id with more than
+// kFixIdsRowCap rows is listed for the bucket launch that follows:
+// {bucket, begin, end, id} from blist[1] on.
+template <int VALUE_KIND, int REC>
+__global__ void __launch_bounds__(kFixIdsThreads) k_fix_ids(KP kp, const unsigned* __restrict__ list,
+                                                            const unsigned* __restrict__ sctl,
+                                                            const unsigned* __restrict__ seg,
+                                                            const RecKey<REC == kRecCompact>* __restrict__ keys,
+                                                            const unsigned* __restrict__ rows,
+                                                            const void* __restrict__ value, PairRecords rec,
+                                                            IdMarks mk, unsigned* __restrict__ id_pos,
+                                                            unsigned* __restrict__ blist, unsigned* err) {
+  constexpr int kWaves = kFixIdsThreads / 64;
+  __shared__ unsigned long long s_sk[kWaves][kFixIdsEntries];
+  __shared__ unsigned s_cnt[kWaves][kFixIdsEntries];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l0 = kp.l0, linf = kp.linf;  // l0 * (1 + linf) <= kFixIdsEntries (the plan)
+  unsigned long long* sk = s_sk[wave];   // [l0] pair sketch
+  unsigned long long* rsk = sk + l0;     // [linf][l0] row sketches
+  unsigned* cnt = s_cnt[wave];           // [l0] rows per kept pair
+  const int flags = kp.clip.flags;
+  const int64_t n_ids = sctl[0];
+  const uint64_t lmask = ((uint64_t)1 << kp.bucket_bits) - 1;
+  for (int64_t j = (int64_t)blockIdx.x * kWaves + wave; j < n_ids; j += (int64_t)gridDim.x * kWaves) {  // wave-uniform
+    const int64_t id = list[j];
+    const int64_t begin = seg[2 * j], end = seg[2 * j + 1];
+    if (end - begin > (int64_t)kFixIdsRowCap) {
+      if (lane == 0) {
+        unsigned* e = blist + 1 + 4 * (int64_t)atomicAdd(blist, 1u);
+        e[0] = (unsigned)(id >> kp.bucket_bits);
+        e[1] = (unsigned)begin;
+        e[2] = (unsigned)end;
+        e[3] = (unsigned)id;
+      }
+      continue;
+    }
+    if (lane < l0) {
+      sk[lane] = kEmpty;
+      cnt[lane] = 0;
+    }
+    if (lane < l0 * linf) rsk[lane] = kEmpty;
+    wave_lds_fence();
+    const uint32_t h = pid_hash(kp.seed, id);
+    const uint64_t local = (uint64_t)id & lmask;
+    // record i -> its pair key (kEmpty: dead) and row
+    auto record = [&](int64_t i, uint32_t* r) -> uint64_t {
+      const RecKey<REC == kRecCompact> v = keys[i];
+      if constexpr (REC == kRecP64) {
+        *r = (uint32_t)((uint64_t)v >> kp.row_shift);
+        if (v == ~0ULL) return kEmpty;
+      } else {
+        *r = rows[i];
+        if (v >> (8 * sizeof(v) - 1)) return kEmpty;
+      }
+      if constexpr (REC == kRecCompact)  // expand_key: rand_shift <= 31
+        return ((uint64_t)pair_hash_from(h, kp.seed, (int64_t)(v & (uint32_t)kp.pk_mask)) << 32) |
+               (v & ((1u << kp.rand_shift) - 1));
+      else
+        return pair_key_from(h, kp.seed, (int64_t)(v & kp.pk_mask), local << kp.pk_bits, kp.rand_shift);
+    };
+    for (int64_t i0 = begin; i0 < end; i0 += 64) {  // B1
+      uint32_t r;
+      const uint64_t x = i0 + lane < end ? record(i0 + lane, &r) : kEmpty;
+      if (x != kEmpty && x < sk[l0 - 1]) sketch_insert_strided(sk, l0, 1, x);
+    }
+    wave_lds_fence();
+    if (kp.sieve_mark && sk[l0 - 1] == kEmpty) {  // wave-uniform: still short of l0 pairs
+      if (lane == 0) {
+        atomicOr(mk.bits + (id >> 5), 1u << (id & 31));
+        const unsigned at = atomicAdd(mk.sctl, 1u);
+        mk.list[at] = (unsigned)id;
+        id_pos[id] = at;
+        mk.seg[2 * (int64_t)at + 1] = 0;
+      }
+      wave_lds_fence();  // the sketch is the next id's
+      continue;
+    }
+    for (int64_t i0 = begin; i0 < end; i0 += 64) {  // B2
+      uint32_t r = 0;
+      const uint64_t x = i0 + lane < end ? record(i0 + lane, &r) : kEmpty;
+      if (x == kEmpty || dead_key(x, kp.rand_shift)) continue;
+      const int s = sketch_find_strided(sk, l0, 1, x);
+      if (s < 0) continue;
+      if (r >= (uint64_t)kp.n) {  // malformed record: flagged, never dereferenced
+        atomicOr(err, 1u);
+        continue;
+      }
+      atomicAdd(cnt + s, 1u);
+      const uint64_t y = row_key(kp.row_seed, kp.row_offset + r, r);
+      unsigned long long* rs = rsk + s;
+      if (y < rs[(linf - 1) * l0]) sketch_insert_strided(rs, linf, l0, y);
+    }
+    wave_lds_fence();
+    if constexpr (VALUE_KIND != PDP_VALUE_NONE) {  // B2.5: entry t of slot s is lane t * l0 + s
+      const bool live = lane < l0 * linf && sk[lane % l0] != kEmpty && (unsigned)(lane / l0) < cnt[lane % l0];
+      if (live) rsk[lane] = (unsigned long long)((const long long*)value)[(uint32_t)rsk[lane]];
+      wave_lds_fence();
+    }
+    bool out = false;  // B3
+    int64_t p = 0;
+    PairSums ps{};
+    if (lane < l0) {
+      const uint64_t x = sk[lane];
+      const unsigned c = cnt[lane];
+      if (x != kEmpty && c != 0) {
+        p = (int64_t)(x & kp.pk_mask);
+        if (p >= kp.P) {  // malformed record: flagged, skipped
+          atomicOr(err, 1u);
+        } else {
+          out = true;
+          ps = pair_sums_from_rows<VALUE_KIND>(rsk + lane, c < (unsigned)linf ? (long long)c : (long long)linf,
+                                               nullptr, kp.clip, l0);
+        }
+      }
+    }
+    const unsigned long long mo = __ballot(out);
+    if (mo) {  // wave-uniform
+      unsigned base = 0;
+      if (lane == 0) base = atomicAdd(rec.flat_n, (unsigned)__popcll(mo));
+      base = __shfl(base, 0, 64);
+      const int64_t at = (int64_t)base + __popcll(mo & ((1ULL << lane) - 1));
+      if (out && at < rec.flat_cap) {  // (<= l0 pairs per id: the list cannot fill)
+        const int64_t i = rec.flat_base + at;
+        rec.key[i] = ((unsigned long long)p << 32) | (unsigned long long)(uint32_t)ps.count;
+        if (flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION))
+          rec.f0[i] = (flags & PDP_SUM_INT) ? __longlong_as_double(ps.isum) : ps.fsum;
+        if (flags & PDP_ACC_NSUM) rec.f1[i] = ps.nsum;
+        if (flags & PDP_ACC_NSUM2) rec.f2[i] = ps.nsum2;
+      }
+    }
+    wave_lds_fence();  // the sketch is the next id's
+  }
+}
+
 
 // ---------------------------------------------------------- launchers --
 int launch_global_rows(const pdp_bound_config* cfg, const KP& kp, hipStream_t st, const int64_t* pid,
@@ -2954,6 +3257,8 @@ struct Marks {
   unsigned* sctl;
   const unsigned* prev;
   unsigned long long* fix_rec;
+  unsigned* pos;  // per-id fix-up: id_pos and the list's row counts (Ws.id_seg / id_seg2), else NULL
+  unsigned* seg;
 };
 
 template <int VK, bool KA>
@@ -2966,16 +3271,20 @@ int launch_bucket_kernel(const KP& kp, const Plan& p, hipStream_t st, const void
   return with_rec(rec_of(p.key_format), [&](auto kind) {
     constexpr int REC = decltype(kind)::value;
     using K = RecKey<REC == kRecCompact>;
-    const auto kern = ranges ? k_bucket_bound<VK, KA, true, REC> : k_bucket_bound<VK, KA, false, REC>;
+    const auto kern = kp.fix_ids ? k_bucket_bound<VK, KA, true, REC, true>
+                      : ranges   ? k_bucket_bound<VK, KA, true, REC>
+                                 : k_bucket_bound<VK, KA, false, REC>;
     const int rc = allow_dynamic_lds(kern, (size_t)p.lds_bytes);
     if (rc != PDP_OK) return rc;
     // a listed launch (fix-ups): a persistent grid of one workgroup per CU (the
     // bucket LDS allows no more) looping over the listed buckets
-    const int64_t grid = blist != nullptr ? std::min<int64_t>(p.n_buckets, device_cus()) : p.n_buckets;
+    // (the per-id fix-up's: up to two of its ids over the row cap per bucket at once)
+    const int64_t grid = blist != nullptr ? std::min<int64_t>(kp.fix_ids ? 2 * p.n_buckets : p.n_buckets, device_cus())
+                                          : p.n_buckets;
     return launch(name, kern, dim3((unsigned)grid), dim3((unsigned)p.bucket_threads), (size_t)p.lds_bytes, st, kp,
                   (const K*)keys, rows, offsets, value, acc, rec, (K*)(ws + w.cand_key),
                   (unsigned*)(ws + w.cand_idx), mk.bits, mk.list, mk.sctl, (unsigned*)(ws + w.err), mk.fix_rec,
-                  mk.prev, blist);
+                  mk.prev, blist, mk.pos, mk.seg);
   });
 }
 
@@ -2995,9 +3304,12 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
                       const Ws& w) {
   const PairRecords rec = pair_records(ws, w, p);
   unsigned long long* fix_rec = (unsigned long long*)(ws + w.fix_rec);  // level-1 blocks are dead
+  unsigned* id_pos = p.fix_ids ? (unsigned*)(ws + w.id_pos) : nullptr;
+  unsigned* seg1 = p.fix_ids ? (unsigned*)(ws + w.id_seg) : nullptr;
+  unsigned* seg2 = p.fix_ids && p.band ? (unsigned*)(ws + w.id_seg2) : nullptr;
   Marks m1{w.unres_bits ? (unsigned*)(ws + w.unres_bits) : nullptr,
            w.unres_list ? (unsigned*)(ws + w.unres_list) : nullptr, w.sctl ? (unsigned*)(ws + w.sctl) : nullptr,
-           nullptr, p.band ? fix_rec : nullptr};
+           nullptr, p.band ? fix_rec : nullptr, id_pos, seg1};
   int rc = launch_bucket_kernel<VK, KA>(kp, p, st, ws + w.keys2, (const unsigned*)(ws + w.rows2),
                                         (const unsigned*)(ws + w.counts), value, acc, rec, ws, w, "k_bucket_bound", m1);
   if (rc != PDP_OK || !p.sieve) return rc;
@@ -3041,6 +3353,43 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
     return launch_bucket_kernel<VK, KA>(kf, pf, st, ws + w.keys2, (const unsigned*)(ws + w.rows2),
                                         (const unsigned*)fix_cnt, value, acc, fr, ws, w, name, mk, blist);
   };
+  // the same per privacy id (Plan.fix_ids): exact test + rows per id -> id
+  // order -> one wave per listed id (`list`, its rows' bounds in `seg`),
+  // whose kept pairs go to the flat list after the main launch's records;
+  // ids over the row cap -> a listed bucket launch (empty unless there is one)
+  auto fixup_ids = [&](unsigned* bits, const unsigned* list, unsigned* sctl, unsigned* seg, const Marks& mk, int mark,
+                       const char* name) -> int {
+    unsigned* blist = (unsigned*)(ws + w.fix_blist);
+    unsigned* err = (unsigned*)(ws + w.err);
+    int r = launch("k_fix_filter", k_fix_id_count, dim3(grid_for(kp.n, 1024)), dim3(kBlock), 0, st, kp, bits, sctl,
+                   fix_rec, id_pos, seg, err, blist);
+    if (r != PDP_OK) return r;
+    r = launch("k_fix_alloc", k_fix_id_alloc, dim3(1), dim3(kBlock), 0, st, sctl, seg);
+    if (r != PDP_OK) return r;
+    KP kf = kp;
+    kf.sieve_mark = mark;
+    kf.sieve_emit = 0;
+    r = with_rec(rec_of(p.key_format), [&](auto kind) {
+      constexpr int REC = decltype(kind)::value;
+      using K = RecKey<REC == kRecCompact>;
+      int r2 = launch("k_fix_scatter", k_fix_id_scatter<REC>, dim3(grid_for(kp.n, 2048)), dim3(kBlock), 0, st, kp, pk,
+                      allowed, fix_rec, sctl, id_pos, seg, (K*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
+      if (r2 != PDP_OK) return r2;
+      const IdMarks im{mk.bits, mk.list, mk.sctl, mk.seg};
+      // persistent: four ids per workgroup at a time, up to 8 workgroups per CU
+      const int64_t ids = p.n_buckets << p.bucket_bits;
+      const int64_t grid = std::min<int64_t>((ids + 3) / 4, 8 * device_cus());
+      return launch("k_fix_ids", k_fix_ids<VK, REC>, dim3((unsigned)grid), dim3(kFixIdsThreads), 0, st, kf,
+                    list, sctl, seg, (const K*)(ws + w.keys2), (const unsigned*)(ws + w.rows2), value, rec, im, id_pos,
+                    blist, err);
+    });
+    if (r != PDP_OK) return r;
+    kf.fix_ids = 1;
+    Plan pf = p;
+    if (p.n_ranges <= kBucketThreads / 2) pf.bucket_threads = kBucketThreads / 2;
+    return launch_bucket_kernel<VK, KA>(kf, pf, st, ws + w.keys2, (const unsigned*)(ws + w.rows2), nullptr, value, acc,
+                                        rec, ws, w, name, mk, blist);
+  };
   auto rescan = [&](const unsigned* bits, const unsigned* list, unsigned* sctl) {
     return launch("k_sieve_rescan", kp.keys_vec ? k_sieve_rescan<true> : k_sieve_rescan<false>, dim3(kRescanBlocks),
                   dim3(kRescanThreads), 0, st, kp, pid, bits, list, sctl, fix_rec);
@@ -3048,10 +3397,12 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
   unsigned* sctl = (unsigned*)(ws + w.sctl);
   unsigned* fix_cnt = (unsigned*)(ws + w.fix_cnt);
   unsigned* fix_cur = (unsigned*)(ws + w.fix_cur);
-  const Marks none{m1.bits, m1.list, m1.sctl, nullptr, nullptr};
+  const Marks none{m1.bits, m1.list, m1.sctl, nullptr, nullptr, nullptr, nullptr};
   if (!p.band) {
     rc = rescan(m1.bits, m1.list, sctl);
     if (rc != PDP_OK) return rc;
+    if constexpr (!KA)
+      if (p.fix_ids) return fixup_ids(m1.bits, m1.list, sctl, seg1, none, 0, "k_bucket_fix");
     return fixup(m1.bits, sctl, fix_cnt, fix_cur, 1, none, 0, "k_bucket_fix");
   }
   // the band: its lists (Bloom filter unless too many ids) -> fix-up launch
@@ -3061,7 +3412,16 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
               fix_rec);
   if (rc != PDP_OK) return rc;
   unsigned* sctl2 = (unsigned*)(ws + w.sctl2);
-  const Marks m2{(unsigned*)(ws + w.unres2_bits), (unsigned*)(ws + w.unres2_list), sctl2, m1.bits, nullptr};
+  const Marks m2{(unsigned*)(ws + w.unres2_bits), (unsigned*)(ws + w.unres2_list), sctl2, m1.bits, nullptr, id_pos, seg2};
+  if constexpr (!KA) {
+    if (p.fix_ids) {
+      rc = fixup_ids(m1.bits, m1.list, sctl, seg1, m2, 1, "k_bucket_fix");
+      if (rc != PDP_OK) return rc;
+      rc = rescan(m2.bits, m2.list, sctl2);
+      if (rc != PDP_OK) return rc;
+      return fixup_ids(m2.bits, m2.list, sctl2, seg2, m2, 0, "k_bucket_fix2");
+    }
+  }
   rc = fixup(m1.bits, sctl, fix_cnt, fix_cur, 1, m2, 1, "k_bucket_fix");
   if (rc != PDP_OK) return rc;
   rc = rescan(m2.bits, m2.list, sctl2);
@@ -3358,7 +3718,7 @@ int pdp_bound_plan(const pdp_bound_config* cfg, pdp_bound_plan_info* info) {
   info->sieve_threads = p.sieve ? p.sieve_threads : 0;
   info->bucket_threads = p.bucket_threads;
   info->hist_u16 = p.algorithm == PDP_ALGO_BUCKETED && p.l1_local ? p.hist_u16 : 0;
-  info->reserved = 0;
+  info->fix_ids = p.algorithm == PDP_ALGO_BUCKETED ? p.fix_ids : 0;
   return PDP_OK;
 }
 
@@ -3427,14 +3787,18 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
     };
     add(w.err, 4, 0u);
     if (p.l1_local) add(w.tile_over, p.n_tiles, ~0u);
-    if (p.merge == PDP_MERGE_RANGES && p.sieve) {
-      add(w.sctl, 4, 0u);
+    if (p.merge == PDP_MERGE_RANGES && p.sieve) add(w.sctl, 4, 0u);
+    if (p.merge == PDP_MERGE_RANGES && p.sieve && !p.fix_ids) {
       add(w.fix_cnt, p.n_buckets + 1, 0u);
       add(w.fix_cur, p.n_buckets, 0u);
     }
-    if (p.merge == PDP_MERGE_RANGES && p.band) {
+    if (p.merge == PDP_MERGE_RANGES && p.band && !p.fix_ids) {
       add(w.fix_cnt2, p.n_buckets + 1, 0u);
       add(w.fix_cur2, p.n_buckets, 0u);
+    }
+    if (p.fix_ids) {  // {unused, fix-up pairs}; the second bitmap is set bit by bit
+      add(w.fix_ctl, 4, 0u);
+      if (p.band) add(w.unres2_bits, (p.n_buckets << p.bucket_bits) / 32, 0u);
     }
     const int rcf = launch_fills(f, st);
     if (rcf != PDP_OK) return rcf;

@@ -78,6 +78,35 @@ __device__ __forceinline__ unsigned item_order(unsigned i, unsigned n) {
   return (unsigned)(((uint64_t)i * 2147483647ull) % (uint64_t)n);
 }
 
+// The per-id fix-up's kept pairs (PairRecords.flat_n of them from flat_base
+// on: a few thousand, in no order) straight into the accumulators, a
+// grid-stride share per workgroup of the reduce launch -- the first few
+// workgroups take them all, the others read the count and go on.
+__device__ __forceinline__ void add_flat_pairs(const KP& kp, const PairRecords& rec,
+                                               const pdp_partition_accumulators& acc, unsigned* err) {
+  if (rec.flat_n == nullptr) return;
+  const int flags = kp.clip.flags;
+  int64_t n = *rec.flat_n;
+  if (n > rec.flat_cap) n = rec.flat_cap;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t o = rec.flat_base + i;
+    const unsigned long long key = rec.key[o];
+    const int64_t p = (int64_t)(key >> 32);
+    if (p >= kp.P) {  // malformed workspace: flagged, skipped
+      atomicOr(err, 1u);
+      continue;
+    }
+    PairSums ps{(long long)(uint32_t)key, 0, 0.0, 0.0, 0.0};
+    if (flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION)) {
+      if (flags & PDP_SUM_INT) ps.isum = __double_as_longlong(rec.f0[o]);
+      else ps.fsum = rec.f0[o];
+    }
+    if (flags & PDP_ACC_NSUM) ps.nsum = rec.f1[o];
+    if (flags & PDP_ACC_NSUM2) ps.nsum2 = rec.f2[o];
+    add_pair_to_partition(acc, p, ps, flags);
+  }
+}
+
 __global__ void __launch_bounds__(kReduceThreads) k_range_reduce(KP kp, PairRecords rec, const uint4* __restrict__ items,
                                                                const unsigned* __restrict__ n_items,
                                                                pdp_partition_accumulators acc, unsigned* err) {
@@ -90,6 +119,7 @@ __global__ void __launch_bounds__(kReduceThreads) k_range_reduce(KP kp, PairReco
   unsigned* cn = pc + kRangeParts;                    // [kRangeParts] row count
   unsigned* pre = cn + kRangeParts;                   // [kReduceThreads] run prefix
   unsigned* wsum = pre + kReduceThreads;              // block-scan scratch
+  add_flat_pairs(kp, rec, acc, err);
   const unsigned n_it = *n_items;
   if (blockIdx.x >= n_it) return;  // grid is an upper bound on the item count
   const unsigned iw = item_order(blockIdx.x, n_it);
@@ -472,13 +502,15 @@ __global__ void __launch_bounds__(kBlock) k_fine_plan(KP kp, const unsigned* __r
 // summed in LDS (or added directly when few), then coalesced atomics
 __global__ void __launch_bounds__(kReduceThreads) k_fine_reduce(KP kp, PairRecords stg, const uint4* __restrict__ items,
                                                               const unsigned* __restrict__ n_items,
-                                                              pdp_partition_accumulators acc, unsigned* err) {
+                                                              pdp_partition_accumulators acc, unsigned* err,
+                                                              PairRecords rec) {
   extern __shared__ unsigned long long smem[];
   double* s0 = (double*)smem;
   double* s1 = s0 + kRangeParts;
   double* s2 = s1 + kRangeParts;
   unsigned* pc = (unsigned*)(s2 + kRangeParts);
   unsigned* cn = pc + kRangeParts;
+  add_flat_pairs(kp, rec, acc, err);  // (`rec`: the bucket kernels' records, for their flat list only)
   if (blockIdx.x >= *n_items) return;
   const uint4 it = items[blockIdx.x];
   const int64_t p0 = (int64_t)it.x << kRangeBits;
@@ -576,7 +608,8 @@ int launch_merge(const KP& kp0, const Plan& p, hipStream_t st, char* ws, const W
   uint4* items = (uint4*)(ws + w.rr_items);
   unsigned* n_items = (unsigned*)(ws + w.rr_count);
   PDP_HIP_CHECK(hipMemsetAsync(n_items, 0, 4, st));
-  const unsigned* last_ids = p.band ? (const unsigned*)(ws + w.sctl2) : nullptr;
+  // (the per-id fix-up writes no record segments: one segment, nothing to skip)
+  const unsigned* last_ids = p.band && !p.fix_ids ? (const unsigned*)(ws + w.sctl2) : nullptr;
   rc = launch("k_range_plan", k_range_plan, dim3((unsigned)p.n_ranges), dim3(kRangeThreads), 0, st, kp, rec.runs, items,
               n_items, last_ids, (int64_t)p.n_buckets);
   if (rc != PDP_OK) return rc;
@@ -611,7 +644,7 @@ int launch_merge(const KP& kp0, const Plan& p, hipStream_t st, char* ws, const W
               fitems, n_fitems);
   if (rc != PDP_OK) return rc;
   return launch_big_lds("k_fine_reduce", k_fine_reduce, dim3((unsigned)p.fine_items), dim3(kReduceThreads), kFineLds,
-                        st, kp, stg, fitems, n_fitems, acc, err);
+                        st, kp, stg, fitems, n_fitems, acc, err, rec);
 }
 
 }  // namespace pdp

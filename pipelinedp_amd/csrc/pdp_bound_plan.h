@@ -61,6 +61,17 @@ constexpr int kReduceThreads = 512;
 constexpr int kSplitThreads = 512;  // k_split_count / k_split_scatter workgroups
 constexpr size_t kRangeLds = kRangeParts * (3 * 8 + 2 * 4) + kReduceThreads * (8 + 4) + (kReduceThreads / 64 + 1) * 4;
 constexpr int kQueueCap = 128;                // per-wave candidate queue (bucket kernel)
+// per-id sieve fix-up (k_fix_ids, Plan.fix_ids): one wave per unresolved
+// privacy id, its pair sketch (l0 entries) and row sketches (l0 * linf) in a
+// per-wave LDS slice of kFixIdsEntries u64 (C2 (8, 2): 24, C4/C5 (4, 2): 12,
+// C3 (2, 1): 4); an id with more fix-up rows than kFixIdsRowCap goes to a
+// listed bucket launch instead.  A wave takes 64 rows per trip and two passes,
+// about 1 us per 64 rows when the rows sit in L2: 4,096 rows cost ~60 us,
+// what a bucket workgroup spends on its fixed LDS set-up and slot sweeps, and
+// past that the bucket's 8 waves on one id's rows win
+constexpr int kFixIdsEntries = 32;
+constexpr unsigned kFixIdsRowCap = 4096;
+constexpr int kFixIdsThreads = 256;
 constexpr int kScanItems = 16;
 constexpr int kScanChunk = kBlock * kScanItems;
 
@@ -94,6 +105,8 @@ struct Plan {
   int bucket_threads;   // k_bucket_bound workgroup: 1,024 or 512 threads (half-size buckets)
   int slot_bits;        // level-1 blocks per tile = 2^slot_bits (kStagesPerTile, or SieveShape::kSlots)
   int hist_u16;         // tile-local level 1 counts buckets in u16 halves (counts_tm / counts_tm2)
+  int fix_ids;          // sieve fix-up per privacy id (k_fix_ids) instead of by bucket launches
+  int64_t pair_slots;   // pair records of one bucket's block: l0 << bucket_bits
 };
 
 struct Ws {
@@ -121,6 +134,10 @@ struct Ws {
   // their rescan's per-bucket counts / cursors
   uint64_t band, band_cnt, unres2_bits, unres2_list, sctl2, fix_cnt2, fix_cur2;
   uint64_t fix_blist;  // fix-up bucket launches: {count, buckets holding fix-up rows...}
+  // per-id fix-up: list position of an unresolved id (valid for listed ids
+  // only), {start, end} of a listed id's fix-up rows per list position for
+  // the first and the second list, {unused, fix-up pairs}
+  uint64_t id_pos, id_seg, id_seg2, fix_ctl;
   uint64_t tile_over;  // tile-local level 1: per tile, the bucket holding all 65,536 of its rows (else ~0)
   // bucketed PDP_MERGE_RANGES: pair records per bucket block, grouped by range
   uint64_t runs, rec_key, rec_f0, rec_f1, rec_f2;
@@ -154,6 +171,7 @@ struct KP {  // kernel parameters
   int slot_bits;        // level-1 blocks per tile = 2^slot_bits (Plan.slot_bits)
   int64_t fix_cap;      // sieve: entries the fix-up row list (fix_rec, Ws.fix_rec) holds
   int row_shift;        // PACKED64 level-2 records: the row's first bit (pk_bits + bucket_bits)
+  int fix_ids;          // bucket kernel, listed launch of the per-id fix-up: blist holds {bucket, begin, end, id}
 };
 
 struct PairRecords {  // PDP_MERGE_RANGES output of the bucket kernel
@@ -163,6 +181,10 @@ struct PairRecords {  // PDP_MERGE_RANGES output of the bucket kernel
   double* f0;                    // sum (int64 bits with PDP_SUM_INT)
   double* f1;                    // normalized sum
   double* f2;                    // normalized sum of squares
+  // per-id fix-up: its kept pairs, a flat list of *flat_n records from
+  // flat_base on (after the buckets' blocks), added by the reduce kernels
+  unsigned* flat_n;
+  int64_t flat_base, flat_cap;
 };
 
 inline PairRecords pair_records(char* ws, const Ws& w, const Plan& p) {
@@ -174,6 +196,11 @@ inline PairRecords pair_records(char* ws, const Ws& w, const Plan& p) {
     rec.f0 = w.rec_f0 ? (double*)(ws + w.rec_f0) : nullptr;
     rec.f1 = w.rec_f1 ? (double*)(ws + w.rec_f1) : nullptr;
     rec.f2 = w.rec_f2 ? (double*)(ws + w.rec_f2) : nullptr;
+    if (p.fix_ids) {
+      rec.flat_n = (unsigned*)(ws + w.fix_ctl) + 1;
+      rec.flat_cap = p.n_buckets * p.pair_slots;
+      rec.flat_base = rec.flat_cap;
+    }
   }
   return rec;
 }
