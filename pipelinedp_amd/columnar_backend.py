@@ -452,7 +452,9 @@ def _to_local_noise_kind(kind):
 
 
 def _is_int(x) -> bool:
-    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+    # (an integer whose fp64 image is outside int64 is no int64 bound: PDP_SUM_INT
+    # refuses it, and the fp64 sum is taken instead)
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool) and -2.0**63 <= float(x) < 2.0**63
 
 
 # -------------------------------------------------------------- backend --

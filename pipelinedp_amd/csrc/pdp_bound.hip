@@ -501,6 +501,19 @@ int validate(const pdp_bound_config* c) {
     return set_error(PDP_E_INVALID, "bad value_kind");
   if (c->value_kind != PDP_VALUE_I64 && (c->flags & PDP_SUM_INT))
     return set_error(PDP_E_INVALID, "PDP_SUM_INT requires int64 values");
+  if (c->flags & PDP_SUM_INT) {
+    // the kernels clip in int64 with (long long)bound, which C++ defines only
+    // for a bound that is an int64: finite, integral, in [-2^63, 2^63)
+    auto is_int64 = [](double b) {
+      return std::isfinite(b) && b == std::floor(b) && b >= -9223372036854775808.0 && b < 9223372036854775808.0;
+    };
+    const bool per_partition = (c->flags & PDP_SUM_PER_PARTITION) != 0;
+    if (per_partition ? !(is_int64(c->min_sum) && is_int64(c->max_sum))
+                      : !(is_int64(c->min_value) && is_int64(c->max_value)))
+      return set_error(PDP_E_UNSUPPORTED, per_partition
+                                              ? "PDP_SUM_INT requires min_sum / max_sum that are int64 values"
+                                              : "PDP_SUM_INT requires min_value / max_value that are int64 values");
+  }
   if (c->algorithm < PDP_ALGO_AUTO || c->algorithm > PDP_ALGO_PAIR_TABLE)
     return set_error(PDP_E_INVALID, "bad algorithm");
   if (c->merge < PDP_MERGE_AUTO || c->merge > PDP_MERGE_RANGES)
@@ -2498,10 +2511,10 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
           if (flags & PDP_SUM_INT)
             atomicAdd((unsigned long long*)(tot + slot),
                       (unsigned long long)clamp_ll(iv, (long long)kp.clip.lo, (long long)kp.clip.hi));
-          else atomicAdd(tot + slot, fmin(fmax(v, kp.clip.lo), kp.clip.hi));
+          else atomicAdd(tot + slot, clip_f64(v, kp.clip.lo, kp.clip.hi));
         }
         if (flags & (PDP_ACC_NSUM | PDP_ACC_NSUM2)) {
-          const double c = fmin(fmax(v, kp.clip.lo), kp.clip.hi) - kp.clip.mid;
+          const double c = clip_f64(v, kp.clip.lo, kp.clip.hi) - kp.clip.mid;
           if (flags & PDP_ACC_NSUM) atomicAdd(tot + n_slots + slot, c);
           if (flags & PDP_ACC_NSUM2) atomicAdd(tot + 2 * n_slots + slot, c * c);
         }

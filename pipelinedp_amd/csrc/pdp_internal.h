@@ -397,6 +397,12 @@ __device__ __forceinline__ long long clamp_ll(long long v, long long lo, long lo
   return v < lo ? lo : (v > hi ? hi : v);
 }
 
+// np.clip on one fp64 value: a NaN stays NaN (fmin / fmax alone would give
+// the bound), as SumCombiner.create_accumulator's np.clip keeps it.
+__device__ __forceinline__ double clip_f64(double v, double lo, double hi) {
+  return v != v ? v : fmin(fmax(v, lo), hi);
+}
+
 struct ClipParams {
   double lo, hi, mid, min_sum, max_sum;
   int flags;
@@ -421,7 +427,7 @@ __device__ __forceinline__ PairSums pair_sums_from_rows(const unsigned long long
       iv = (long long)rows[t * stride];
       v = VALUE_KIND == PDP_VALUE_I64 ? (double)iv : __longlong_as_double(iv);
     }
-    const double cv = fmin(fmax(v, cp.lo), cp.hi);
+    const double cv = clip_f64(v, cp.lo, cp.hi);
     if (cp.flags & PDP_SUM_PER_PARTITION) {
       raw += v;
       iraw += iv;
@@ -436,7 +442,7 @@ __device__ __forceinline__ PairSums pair_sums_from_rows(const unsigned long long
   }
   if (cp.flags & PDP_SUM_PER_PARTITION) {
     if (cp.flags & PDP_SUM_INT) s.isum = clamp_ll(iraw, (long long)cp.min_sum, (long long)cp.max_sum);
-    else s.fsum = fmin(fmax(raw, cp.min_sum), cp.max_sum);
+    else s.fsum = clip_f64(raw, cp.min_sum, cp.max_sum);
   }
   return s;
 }
@@ -459,10 +465,10 @@ __device__ __forceinline__ void accumulate_row(const void* value, uint32_t row, 
   } else if (flags & PDP_ACC_SUM) {
     if (flags & PDP_SUM_INT)
       atomicAdd((unsigned long long*)(f0 + slot), (unsigned long long)clamp_ll(iv, (long long)cp.lo, (long long)cp.hi));
-    else unsafeAtomicAdd(f0 + slot, fmin(fmax(v, cp.lo), cp.hi));
+    else unsafeAtomicAdd(f0 + slot, clip_f64(v, cp.lo, cp.hi));
   }
   if (flags & (PDP_ACC_NSUM | PDP_ACC_NSUM2)) {
-    const double c = fmin(fmax(v, cp.lo), cp.hi) - cp.mid;
+    const double c = clip_f64(v, cp.lo, cp.hi) - cp.mid;
     if (flags & PDP_ACC_NSUM) unsafeAtomicAdd(f1 + slot, c);
     if (flags & PDP_ACC_NSUM2) unsafeAtomicAdd(f2 + slot, c * c);
   }
@@ -475,7 +481,7 @@ __device__ __forceinline__ PairSums pair_sums_from_totals(long long cnt, double 
   const long long ibits = __double_as_longlong(fsum_or_bits);
   if (cp.flags & PDP_SUM_PER_PARTITION) {
     if (cp.flags & PDP_SUM_INT) s.isum = clamp_ll(ibits, (long long)cp.min_sum, (long long)cp.max_sum);
-    else s.fsum = fmin(fmax(fsum_or_bits, cp.min_sum), cp.max_sum);
+    else s.fsum = clip_f64(fsum_or_bits, cp.min_sum, cp.max_sum);
   } else if (cp.flags & PDP_SUM_INT) {
     s.isum = ibits;
   } else {

@@ -417,7 +417,7 @@ __global__ void __launch_bounds__(kBlock) k_vector_sum_metrics(const double* __r
     }
     for (int j = lane; j < d; j += 64) {
       const double x = v[j];
-      const double c = norm_kind == PDP_NORM_LINF ? fmin(fmax(x, -max_norm), max_norm) : x * coef;
+      const double c = norm_kind == PDP_NORM_LINF ? clip_f64(x, -max_norm, max_norm) : x * coef;
       out[i * d + j] = secure_add_noise(np, c, seed, (partition_offset + p) * d + j, kVectorSumSlot);
     }
   }

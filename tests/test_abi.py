@@ -240,6 +240,32 @@ def test_sum_int_needs_int_values(lib):
     assert rc == -1 and b"PDP_SUM_INT" in lib.pdp_last_error()
 
 
+@pytest.mark.parametrize("bound", [float("nan"), float("inf"), -float("inf"), 2.5, 2.0 ** 63, -(2.0 ** 64)])
+@pytest.mark.parametrize("fields,flags", [(("min_value", "max_value"), N.ACC_SUM | N.SUM_INT),
+                                          (("min_sum", "max_sum"), N.SUM_PER_PARTITION | N.SUM_INT)])
+def test_sum_int_needs_int64_bounds(lib, fields, flags, bound):
+    """With PDP_SUM_INT the kernels clip in int64 with (long long)bound: a
+    bound that is not finite, not integral or outside [-2^63, 2^63) is refused
+    (-4) before any device work; the largest and smallest int64 bounds pass."""
+    info = N.BoundPlanInfo()
+    ok = dict(value_kind=N.VALUE_I64, flags=flags, min_value=0.0, max_value=7.0, min_sum=-3.0, max_sum=9.0)
+    assert lib.pdp_bound_plan(ctypes.byref(_cfg(**ok)), ctypes.byref(info)) == 0
+    edge = dict(ok, **{fields[0]: -(2.0 ** 63), fields[1]: 2.0 ** 63 - 1024.0})
+    assert lib.pdp_bound_plan(ctypes.byref(_cfg(**edge)), ctypes.byref(info)) == 0
+    for f in fields:
+        cfg = _cfg(**dict(ok, **{f: bound}))
+        assert lib.pdp_bound_plan(ctypes.byref(cfg), ctypes.byref(info)) == -4
+        assert b"PDP_SUM_INT" in lib.pdp_last_error() and f.encode() in lib.pdp_last_error()
+        nbytes = ctypes.c_uint64(0)
+        assert lib.pdp_bound_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)) == -4
+        rc = lib.pdp_bound_contributions(ctypes.byref(cfg), None, None, None, None, None, 0, None)
+        assert rc == -4
+    # the other pair of bounds is not cast with these flags: any value passes
+    other = ("min_sum", "max_sum") if fields[0] == "min_value" else ("min_value", "max_value")
+    free = dict(ok, **{other[0]: -float("inf"), other[1]: float("inf")})
+    assert lib.pdp_bound_plan(ctypes.byref(_cfg(**free)), ctypes.byref(info)) == 0
+
+
 def test_null_arguments_are_rejected_before_device_work(lib):
     cfg = _cfg(n_rows=10)
     assert lib.pdp_bound_plan(ctypes.byref(cfg), None) == -1
