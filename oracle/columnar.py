@@ -435,8 +435,12 @@ def select(row_count, strategy, *, max_rows_per_privacy_id=1, pre_threshold=0, k
     return keep, noised
 
 
-def noise_metrics(ops, index, acc, sum_is_int, noised_count, seed, partition_offset=0, n_cols=None):
-    """Restates pdp_noise_metrics. ops: list of dicts with the pdp_metric_op fields."""
+def noise_metrics(ops, index, acc, sum_is_int, noised_count, seed, partition_offset=0, n_cols=None,
+                  variance_terms=None):
+    """Restates pdp_noise_metrics. ops: list of dicts with the pdp_metric_op fields.
+    variance_terms: a dict that receives {op position: (dp_mean, dp_mean_sq)},
+    the two terms of every VARIANCE op's dp_mean_sq - dp_mean * dp_mean (the
+    tests bound that one column's rounding with them)."""
     index = np.asarray(index, dtype=np.int64)
     g = partition_offset + index
     if n_cols is None:
@@ -478,6 +482,8 @@ def noise_metrics(ops, index, acc, sum_is_int, noised_count, seed, partition_off
                 dp_mean = noised(1, acc["normalized_sum"][index], slot + 1) / denom
                 dp_mean_sq = noised(2, acc["normalized_sum_sq"][index], slot + 2) / denom
             dp_var = dp_mean_sq - dp_mean * dp_mean
+            if variance_terms is not None:
+                variance_terms[o] = (dp_mean, dp_mean_sq)
             if not op.get("degenerate", 0):
                 dp_mean = dp_mean + op["middle"]
             put(cols[0], dp_var)

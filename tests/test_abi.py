@@ -327,3 +327,218 @@ def test_sieve_threads_plan(lib):
     assert info.sieve_threads == 0
     nbytes = ctypes.c_uint64(0)
     assert lib.pdp_bound_workspace_bytes(ctypes.byref(_cfg(**c3, sieve_threads=256)), ctypes.byref(nbytes)) == -1
+
+
+# ------------------------------------------------------- the release path --
+# Argument validation of pdp_select.hip's entry points.  Every call below is
+# refused (or, for the one pinned exception, accepted) before any device work;
+# the non-NULL pointers are host dummies that are never dereferenced.
+_DUMMY = ctypes.create_string_buffer(4096 + 16)
+_HOST = (ctypes.addressof(_DUMMY) + 15) & ~15  # 16-byte aligned
+
+
+def _noise(family="laplace", **kw):
+    """A valid mechanism of `family`, then the C fields in kw overwritten."""
+    from pipelinedp_amd import dp_computations as dpc
+    c = {"laplace": dpc.laplace_noise_params(1.0, 1.0), "gaussian": dpc.gaussian_noise_params(2.0)}[family].to_c()
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+BAD_NOISE = [
+    ("laplace", dict(kind=7), b"bad noise kind"),
+    ("laplace", dict(granularity=float("nan")), b"granularity must be finite"),
+    ("laplace", dict(granularity=-1.0), b"granularity must be finite"),
+    ("laplace", dict(scale=-1.0), b"scale must be finite"),
+    ("laplace", dict(scale=float("inf")), b"scale must be finite"),
+    ("laplace", dict(granularity=0.0), b"granularity 0 with a nonzero scale"),
+    ("laplace", dict(lambda_=0.0), b"Laplace noise needs"),
+    ("laplace", dict(lambda_=float("inf")), b"Laplace noise needs"),
+    ("gaussian", dict(step=0), b"Gaussian noise needs"),
+    ("gaussian", dict(step=1 << 32), b"Gaussian noise needs"),
+    ("gaussian", dict(n=1.0), b"Gaussian noise needs"),
+    ("gaussian", dict(bound=0.0), b"Gaussian noise needs"),
+    ("gaussian", dict(coef=float("nan")), b"Gaussian noise needs"),
+]
+_BAD_NOISE_IDS = [f"{k}-{next(iter(kw))}={next(iter(kw.values()))}" for k, kw, _ in BAD_NOISE]
+
+
+def _select_cfg(**kw):
+    c = N.SelectConfig()
+    c.n_partitions, c.strategy, c.max_rows_per_privacy_id = 10, N.SELECT_ALL_NONEMPTY, 1
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def _select(lib, cfg, row_count=_HOST, keep=_HOST):
+    return lib.pdp_select_partitions(None if cfg is None else ctypes.byref(cfg), row_count, keep, None, None)
+
+
+def test_select_partitions_arguments(lib):
+    assert _select(lib, None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert _select(lib, _select_cfg(), keep=None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert _select(lib, _select_cfg(n_partitions=-1)) == -1 and b"n_partitions < 0" in lib.pdp_last_error()
+    for strategy in (-1, 5):
+        assert _select(lib, _select_cfg(strategy=strategy)) == -1 and b"bad strategy" in lib.pdp_last_error()
+    assert _select(lib, _select_cfg(strategy=N.SELECT_PUBLIC)) == -1 and b"public_mask" in lib.pdp_last_error()
+    tg = N.SELECT_TRUNCATED_GEOMETRIC
+    assert _select(lib, _select_cfg(strategy=tg, keep_table_len=4)) == -1 and b"keep_prob" in lib.pdp_last_error()
+    for length in (0, -3):
+        assert _select(lib, _select_cfg(strategy=tg, keep_prob=_HOST, keep_table_len=length)) == -1
+        assert b"keep_prob" in lib.pdp_last_error()
+    for strategy, extra in ((N.SELECT_ALL_NONEMPTY, {}), (tg, dict(keep_prob=_HOST, keep_table_len=4)),
+                            (N.SELECT_LAPLACE_THRESHOLDING, dict(noise=_noise()))):
+        assert _select(lib, _select_cfg(strategy=strategy, **extra), row_count=None) == -1
+        assert b"row_count" in lib.pdp_last_error()
+    # a valid configuration of zero partitions is accepted without a launch
+    assert _select(lib, _select_cfg(n_partitions=0)) == 0
+
+
+@pytest.mark.parametrize("strategy", [N.SELECT_LAPLACE_THRESHOLDING, N.SELECT_GAUSSIAN_THRESHOLDING])
+@pytest.mark.parametrize("kind,fields,msg", BAD_NOISE, ids=_BAD_NOISE_IDS)
+def test_select_partitions_rejects_bad_noise(lib, strategy, kind, fields, msg):
+    """Both thresholding strategies check their mechanism, whichever its kind."""
+    assert _select(lib, _select_cfg(strategy=strategy, noise=_noise(kind, **fields))) == -1
+    assert msg in lib.pdp_last_error()
+    # the other strategies do not read the mechanism
+    assert _select(lib, _select_cfg(n_partitions=0, noise=_noise(kind, **fields))) == 0
+
+
+def test_compact_arguments(lib):
+    need = ctypes.c_uint64(0)
+    assert lib.pdp_compact_workspace_bytes(5000, ctypes.byref(need)) == 0 and need.value == 256
+    assert lib.pdp_compact_workspace_bytes(-1, ctypes.byref(need)) == -1
+    assert lib.pdp_compact_workspace_bytes(10, None) == -1
+    assert lib.pdp_compact(_HOST, -1, _HOST, _HOST, _HOST, 256, None) == -1 and b"bad argument" in lib.pdp_last_error()
+    assert lib.pdp_compact(_HOST, 10, _HOST, None, _HOST, 256, None) == -1 and b"bad argument" in lib.pdp_last_error()
+    assert lib.pdp_compact(_HOST, 10, _HOST, _HOST, None, 256, None) == -3
+    assert b"workspace too small" in lib.pdp_last_error()
+    assert lib.pdp_compact(_HOST, 10, _HOST, _HOST, _HOST, 255, None) == -3
+    # 4,096 elements per block count: 32 x 4,096 + 1 elements need 33 counts = 264 bytes -> 512
+    assert lib.pdp_compact_workspace_bytes(32 * 4096 + 1, ctypes.byref(need)) == 0 and need.value == 512
+    assert lib.pdp_compact(_HOST, 32 * 4096 + 1, _HOST, _HOST, _HOST, 256, None) == -3
+    assert lib.pdp_compact(None, 10, _HOST, _HOST, _HOST, 256, None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert lib.pdp_compact(_HOST, 10, None, _HOST, _HOST, 256, None) == -1 and b"NULL argument" in lib.pdp_last_error()
+
+
+def _acc(**missing):
+    a = N.PartitionAccumulators()
+    for name, _ in N.PartitionAccumulators._fields_:
+        setattr(a, name, None if name in missing else _HOST)
+    return a
+
+
+def _op(kind, **kw):
+    op = N.MetricOp()
+    op.kind = kind
+    for m in range(3):
+        op.noise[m] = _noise()
+    for j in range(4):
+        op.out_col[j] = j
+    for k, v in kw.items():
+        setattr(op, k, v)
+    return op
+
+
+def _metrics(lib, ops, n_ops=None, *, index=_HOST, n_kept=10, acc=None, noised=_HOST, out=_HOST, stride=10,
+             acc_null=False):
+    arr = None if ops is None else (N.MetricOp * max(len(ops), 1))(*ops)
+    n_ops = (0 if ops is None else len(ops)) if n_ops is None else n_ops
+    acc = _acc() if acc is None else acc
+    return lib.pdp_noise_metrics(arr, n_ops, index, n_kept, None, 0, None if acc_null else ctypes.byref(acc), 0,
+                                 noised, out, stride, 1, None)
+
+
+def test_noise_metrics_arguments(lib):
+    count = [_op(N.OP_COUNT)]
+    for n_ops in (-1, 9):
+        assert _metrics(lib, count * 9, n_ops) == -1 and b"bad ops" in lib.pdp_last_error()
+    assert _metrics(lib, None, 1) == -1 and b"bad ops" in lib.pdp_last_error()
+    assert _metrics(lib, count, acc_null=True) == -1 and b"bad ops" in lib.pdp_last_error()
+    assert _metrics(lib, count, n_kept=-1) == -1 and b"n_kept / out_stride" in lib.pdp_last_error()
+    assert _metrics(lib, count, n_kept=10, stride=9) == -1 and b"n_kept / out_stride" in lib.pdp_last_error()
+    assert _metrics(lib, count, index=None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert _metrics(lib, count, out=None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert _metrics(lib, [_op(99)]) == -1 and b"unknown op kind" in lib.pdp_last_error()
+    assert _metrics(lib, [_op(0)]) == -1 and b"unknown op kind" in lib.pdp_last_error()
+    assert _metrics(lib, count + [_op(99)]) == -1 and b"unknown op kind" in lib.pdp_last_error()  # every op is checked
+    assert _metrics(lib, [], 0) == 0  # no ops: nothing to do
+
+
+@pytest.mark.parametrize("kind,missing,msg", [
+    (N.OP_COUNT, "count", b"COUNT needs"), (N.OP_SUM, "sum", b"SUM needs"),
+    (N.OP_PRIVACY_ID_COUNT, "privacy_id_count", b"privacy_id_count"),
+    (N.OP_MEAN, "count", b"MEAN needs"), (N.OP_MEAN, "normalized_sum", b"MEAN needs"),
+    (N.OP_VARIANCE, "count", b"VARIANCE needs"), (N.OP_VARIANCE, "normalized_sum", b"VARIANCE needs"),
+    (N.OP_VARIANCE, "normalized_sum_sq", b"VARIANCE needs"),
+])
+def test_noise_metrics_needs_each_ops_accumulator(lib, kind, missing, msg):
+    assert _metrics(lib, [_op(kind)], acc=_acc(**{missing: True})) == -1
+    assert msg in lib.pdp_last_error()
+
+
+def test_noise_metrics_thresholded_pid_needs_the_noised_count(lib):
+    assert _metrics(lib, [_op(N.OP_THRESHOLDED_PID)], noised=None) == -1
+    assert b"THRESHOLDED_PID needs noised_count" in lib.pdp_last_error()
+
+
+@pytest.mark.parametrize("op_kind,mech", [(N.OP_COUNT, 0), (N.OP_MEAN, 0), (N.OP_MEAN, 1), (N.OP_VARIANCE, 0),
+                                          (N.OP_VARIANCE, 1), (N.OP_VARIANCE, 2)])
+@pytest.mark.parametrize("kind,fields,msg", BAD_NOISE[:1] + BAD_NOISE[5:7] + BAD_NOISE[8:9],
+                         ids=_BAD_NOISE_IDS[:1] + _BAD_NOISE_IDS[5:7] + _BAD_NOISE_IDS[8:9])
+def test_noise_metrics_checks_every_mechanism(lib, op_kind, mech, kind, fields, msg):
+    """MEAN's second and VARIANCE's second and third mechanisms are checked
+    like the first, in an op that is not the first of its list."""
+    op = _op(op_kind)
+    op.noise[mech] = _noise(kind, **fields)
+    assert _metrics(lib, [_op(N.OP_COUNT), op]) == -1
+    assert msg in lib.pdp_last_error()
+
+
+def test_noise_metrics_zero_kept_skips_the_op_checks(lib):
+    """Pins today's order of checks: with n_kept == 0 pdp_noise_metrics returns
+    PDP_OK before it validates the ops, so an unknown kind, a missing
+    accumulator or a bad mechanism pass unnoticed there.  (n_ops, the ops
+    pointer and out_stride are checked first and still refused.)"""
+    bad = _op(N.OP_MEAN)
+    bad.noise[1] = _noise(kind=7)
+    for ops, acc in (([_op(99)], None), ([_op(N.OP_COUNT)], _acc(count=True)), ([bad], None)):
+        assert _metrics(lib, ops, n_kept=0, stride=0, acc=acc) == 0
+        assert _metrics(lib, ops, n_kept=10, acc=acc) == -1
+    assert _metrics(lib, [_op(99)] * 9, n_kept=0, stride=0) == -1
+    assert _metrics(lib, [_op(99)], n_kept=0, stride=-1) == -1
+
+
+def test_add_noise_arguments(lib):
+    ok = _noise()
+    call = lib.pdp_add_noise
+    assert call(_HOST, N.VALUE_F64, -1, ctypes.byref(ok), 1, 0, _HOST, None) == -1 and b"n must be" in lib.pdp_last_error()
+    for kind in (N.VALUE_NONE, 3):
+        assert call(_HOST, kind, 4, ctypes.byref(ok), 1, 0, _HOST, None) == -1 and b"value_kind" in lib.pdp_last_error()
+    assert call(_HOST, N.VALUE_F64, 4, None, 1, 0, _HOST, None) == -1 and b"noise params are NULL" in lib.pdp_last_error()
+    assert call(None, N.VALUE_F64, 4, ctypes.byref(ok), 1, 0, _HOST, None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert call(_HOST, N.VALUE_I64, 4, ctypes.byref(ok), 1, 0, None, None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    for values, out in ((_HOST + 8, _HOST), (_HOST, _HOST + 8), (_HOST + 4, _HOST + 4)):
+        assert call(values, N.VALUE_F64, 4, ctypes.byref(ok), 1, 0, out, None) == -1
+        assert b"16-byte aligned" in lib.pdp_last_error()
+    assert call(None, N.VALUE_I64, 0, ctypes.byref(ok), 1, 0, None, None) == 0  # nothing to do
+
+
+def test_vector_sum_metrics_arguments(lib):
+    ok = _noise()
+
+    def call(d=8, norm=N.NORM_L2, max_norm=1.0, n_kept=4, noise=ok, vacc=_HOST):
+        return lib.pdp_vector_sum_metrics(vacc, d, norm, max_norm, None if noise is None else ctypes.byref(noise),
+                                          _HOST, n_kept, None, 0, _HOST, 1, None)
+    for d in (0, -1, N.MAX_VECTOR_SIZE + 1):
+        assert call(d=d) == -4 and b"vector_size" in lib.pdp_last_error()
+    for norm in (-1, 3):
+        assert call(norm=norm) == -1 and b"norm_kind" in lib.pdp_last_error()
+    for max_norm in (-1.0, float("nan"), -float("inf")):
+        assert call(max_norm=max_norm) == -1 and b"max_norm" in lib.pdp_last_error()
+    assert call(n_kept=-1) == -1 and b"n_kept" in lib.pdp_last_error()
+    assert call(noise=_noise("gaussian", step=0)) == -1 and b"Gaussian noise needs" in lib.pdp_last_error()
+    assert call(vacc=None) == -1 and b"NULL argument" in lib.pdp_last_error()
+    assert call(d=N.MAX_VECTOR_SIZE, n_kept=0) == 0  # the largest size passes the checks; nothing kept: no launch
