@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 17
+#define PDP_ABI_VERSION 18
 
 /* error codes */
 #define PDP_OK 0
@@ -591,6 +591,85 @@ int pdp_filter_rows(const int64_t* privacy_id, const int64_t* partition, const u
  * keeps it below 2^63; a larger upper_bound returns PDP_E_UNSUPPORTED. */
 int pdp_l0_impact_dropped(const int64_t* l0_count, int64_t upper_bound, const int64_t* candidates,
                           int64_t n_candidates, int64_t* dropped, void* stream);
+
+/* Utility analysis, the per-partition stage: what the reference's
+ * UtilityAnalysisEngine.analyze yields per partition
+ * (analysis/per_partition_combiners.py:193-356, CompoundCombiner.compute_metrics)
+ * for n_configurations parameter sets in one pass over the data.  Input: one
+ * row per (privacy id, partition) pair, as analysis/pre_aggregation.py emits
+ * them: partition in [0, n_partitions), count and sum of the pair's rows, and
+ * n_partitions_of_pid, the pair's privacy id's distinct partitions (all device
+ * arrays; sum may be NULL without PDP_UA_SUM).  With public partitions the
+ * reference adds one pair (0, 0, 0) to EVERY public partition
+ * (dp_engine.py:298-313 with CompoundCombiner.create_accumulator(()) :383-388):
+ * the caller appends those rows, and sets PDP_UA_PUBLIC, which skips the
+ * selection probability.
+ *
+ * Per pair and configuration k, q = min(1, l0_k / n_partitions_of_pid), 0 when
+ * that is <= 0; a metric's value x (SUM: sum, bounds [min_sum_k, max_sum_k];
+ * COUNT: count, [0, linf_k]; PRIVACY_ID_COUNT: 1[count > 0], [0, 1]) gives
+ * c = clip(x), and the partition's sums of x, (c - x)[x < lo], (c - x)[x > hi],
+ * -c (1 - q) and c^2 q (1 - q) (SumCombiner.create_accumulator :244-269).
+ *
+ * Outputs (device, caller-owned, row-major, configuration index fastest so
+ * that a wave's 64 lanes = 64 configurations store 512 contiguous bytes):
+ *   raw_statistics   int64[n_partitions][2]: pairs of the partition, sum of count
+ *   keep_probability double[n_partitions][K] (NULL with PDP_UA_PUBLIC)
+ *   metrics          double[M][5][n_partitions][K], M = requested metrics in
+ *                    SUM, COUNT, PRIVACY_ID_COUNT order; the 5 fields are
+ *                    SumMetrics' sum, clipping_to_min_error,
+ *                    clipping_to_max_error, expected_l0_bounding_error,
+ *                    std_l0_bounding_error (the square root of the fifth sum).
+ * A partition without pairs gets zeros and keep table entry 0.
+ *
+ * keep_probability: PartitionSelectionCalculator.compute_probability_to_keep
+ * (:122-151).  A partition of n <= 100 pairs: the exact Poisson-binomial PMF of
+ * its q's (poisson_binomial.compute_pmf); n > 100: the refined normal
+ * approximation from sum q, sum q(1-q), sum q(1-q)(1-2q)
+ * (compute_pmf_approximation, its sigma == 0 branch and mean +- 8 sigma window
+ * included).  Either PMF is dotted with configuration k's keep table,
+ * keep_tables[keep_offsets[k] .. keep_offsets[k + 1]) (device doubles;
+ * keep_offsets: HOST int64[K + 1], keep_offsets[0] = 0): entry i is the
+ * strategy's probability_of_keep(i), tabulated by the host until it is exactly
+ * 1.0; entries past the end count as 1.0.  A table of more than
+ * PDP_UA_MAX_KEEP_TABLE entries is refused (PDP_E_UNSUPPORTED).
+ *
+ * params: HOST array of n_configurations entries; it and keep_offsets are
+ * copied to the workspace by host-to-device copies enqueued on `stream`.
+ * Nothing else synchronises.  No floating-point atomic is used and every
+ * summation order is fixed: two calls on the same input give the same bits.
+ * A partition code outside [0, n_partitions) sets bit 0 of the error word at
+ * the start of the workspace (pdp_bound_error_flags) and the pair is skipped.
+ * n_pairs, n_partitions < 2^31.  The workspace (256-byte aligned) holds the
+ * sorted pair columns (40 B per pair) and, without PDP_UA_PUBLIC, the three
+ * moments (24 B per partition and configuration). */
+#define PDP_MAX_CONFIGURATIONS 1024
+#define PDP_UA_MAX_KEEP_TABLE 1048576
+#define PDP_UA_SUM 0x1
+#define PDP_UA_COUNT 0x2
+#define PDP_UA_PRIVACY_ID_COUNT 0x4
+#define PDP_UA_PUBLIC 0x8 /* public partitions: no selection probability */
+
+typedef struct pdp_ua_config_params {
+  int64_t l0;     /* max_partitions_contributed (>= 1) */
+  int64_t linf;   /* max_contributions_per_partition (COUNT) */
+  double min_sum; /* min_sum_per_partition (SUM) */
+  double max_sum; /* max_sum_per_partition (SUM) */
+} pdp_ua_config_params;
+
+typedef struct pdp_ua_outputs {
+  int64_t* raw_statistics;
+  double* keep_probability;
+  double* metrics;
+} pdp_ua_outputs;
+
+int pdp_utility_analysis_workspace_bytes(int64_t n_pairs, int64_t n_partitions, int32_t n_configurations,
+                                         int32_t flags, uint64_t* bytes);
+int pdp_utility_analysis(const int64_t* partition, const int64_t* count, const double* sum,
+                         const int64_t* n_partitions_of_pid, int64_t n_pairs, int64_t n_partitions,
+                         const pdp_ua_config_params* params, int32_t n_configurations, const double* keep_tables,
+                         const int64_t* keep_offsets, int32_t flags, const pdp_ua_outputs* out, void* workspace,
+                         uint64_t workspace_bytes, void* stream);
 
 /* Multi-GPU sharding check (ColumnarBackend privacy_id_sharding="verify"):
  * counts the ids whose owner rank is not `rank`, where owner(id) =

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PIPELINEDP_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "lib", "libpipelinedp_amd.so")
 
 # constants (include/pipelinedp_amd.h)
-ABI_VERSION = 17
+ABI_VERSION = 18
 VALUE_NONE, VALUE_F64, VALUE_I64 = 0, 1, 2
 ACC_SUM, ACC_NSUM, ACC_NSUM2, SUM_PER_PARTITION, SUM_INT = 0x1, 0x2, 0x4, 0x8, 0x10
 DEBUG_CORRUPT_RECORDS = 0x40000000  # tests only (pipelinedp_amd.h)
@@ -39,6 +39,9 @@ MAX_OPS = 8
 MAX_VECTOR_SIZE = 4096      # PDP_MAX_VECTOR_SIZE
 NORM_LINF, NORM_L1, NORM_L2 = 0, 1, 2
 VECTOR_SUM_SLOT = 0x56454353  # Philox slot of the vector-sum noise ("VECS")
+MAX_CONFIGURATIONS = 1024   # PDP_MAX_CONFIGURATIONS (utility analysis)
+UA_MAX_KEEP_TABLE = 1 << 20
+UA_SUM, UA_COUNT, UA_PRIVACY_ID_COUNT, UA_PUBLIC = 0x1, 0x2, 0x4, 0x8
 
 EXPORTED_SYMBOLS = (
     "pdp_abi_version",
@@ -70,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "pdp_filter_rows_workspace_bytes",
     "pdp_filter_rows",
     "pdp_l0_impact_dropped",
+    "pdp_utility_analysis_workspace_bytes",
+    "pdp_utility_analysis",
     "pdp_bound_error_flags",
     "pdp_bound_error_flags_async",
     "pdp_owner_mismatches",
@@ -219,6 +224,18 @@ class HistogramBins(ctypes.Structure):
         "float_lowers", "float_n_lowers")]
 
 
+class UaConfigParams(ctypes.Structure):
+    """pdp_ua_config_params: one utility-analysis parameter configuration."""
+    _fields_ = [("l0", ctypes.c_int64), ("linf", ctypes.c_int64),
+                ("min_sum", ctypes.c_double), ("max_sum", ctypes.c_double)]
+
+
+class UaOutputs(ctypes.Structure):
+    """pdp_ua_outputs: device output arrays of pdp_utility_analysis (caller-owned)."""
+    _fields_ = [("raw_statistics", ctypes.c_void_p), ("keep_probability", ctypes.c_void_p),
+                ("metrics", ctypes.c_void_p)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -268,6 +285,9 @@ def signatures():
         "pdp_filter_rows_workspace_bytes": (ctypes.c_int, [i64, P(u64)]),
         "pdp_filter_rows": (ctypes.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, vp, u64, vp]),
         "pdp_l0_impact_dropped": (ctypes.c_int, [vp, i64, vp, i64, vp, vp]),
+        "pdp_utility_analysis_workspace_bytes": (ctypes.c_int, [i64, i64, i32, i32, P(u64)]),
+        "pdp_utility_analysis": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, P(UaConfigParams), i32, vp, P(i64), i32,
+                                                P(UaOutputs), vp, u64, vp]),
         "pdp_bound_error_flags": (ctypes.c_int, [vp, P(ctypes.c_uint32), vp]),
         "pdp_bound_error_flags_async": (ctypes.c_int, [vp, vp, vp]),
         "pdp_owner_mismatches": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),

@@ -7,6 +7,7 @@ parameters of the GPU selection kernel (``device_spec``); the per-partition
 keep decisions and noise draws run in ``k_select`` (csrc/pdp_kernels.hip).
 The host methods (should_keep etc.) exist for API parity and single values.
 """
+import math
 from typing import Optional
 
 import numpy as np
@@ -86,6 +87,17 @@ class _ThresholdingPartitionSelection(PartitionSelectionStrategy):
     def should_keep(self, n: int) -> bool:
         return self.noised_value_if_should_keep(n) is not None
 
+    def probability_of_keep(self, n: int) -> float:
+        """P(noise(m) > threshold) for the shifted count m: the survival
+        function of the continuous mechanism at threshold - m."""
+        m = self._shifted(n)
+        if m is None:
+            return 0.0
+        return self._survival(float(m) - self.threshold)
+
+    def _survival(self, x: float) -> float:
+        raise NotImplementedError
+
     def device_spec(self, max_rows_per_privacy_id: int = 1):
         from pipelinedp_amd.executor import SelectionSpec
         return SelectionSpec(strategy=self._kernel_strategy,
@@ -103,6 +115,10 @@ class LaplacePartitionSelection(_ThresholdingPartitionSelection):
             self.epsilon, self.delta, self.max_partitions_contributed)
         self.noise = dpc.laplace_noise_params(self.epsilon, self.max_partitions_contributed)
 
+    def _survival(self, x: float) -> float:
+        b = self.noise_scale
+        return 0.5 * math.exp(x / b) if x <= 0 else 1.0 - 0.5 * math.exp(-x / b)
+
 
 class GaussianPartitionSelection(_ThresholdingPartitionSelection):
     _kernel_strategy = N.SELECT_GAUSSIAN_THRESHOLDING
@@ -112,6 +128,9 @@ class GaussianPartitionSelection(_ThresholdingPartitionSelection):
         self.noise_scale, self.threshold = dpc.gaussian_thresholding_params(
             self.epsilon, self.delta, self.max_partitions_contributed)
         self.noise = dpc.gaussian_noise_params(self.noise_scale)
+
+    def _survival(self, x: float) -> float:
+        return 0.5 * math.erfc(-x / (self.noise_scale * math.sqrt(2.0)))
 
 
 _CLASSES = {
