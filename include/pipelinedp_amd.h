@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 18
+#define PDP_ABI_VERSION 19
 
 /* error codes */
 #define PDP_OK 0
@@ -670,6 +670,55 @@ int pdp_utility_analysis(const int64_t* partition, const int64_t* count, const d
                          const pdp_ua_config_params* params, int32_t n_configurations, const double* keep_tables,
                          const int64_t* keep_offsets, int32_t flags, const pdp_ua_outputs* out, void* workspace,
                          uint64_t workspace_bytes, void* stream);
+
+/* Utility analysis, the cross-partition stage: what the reference's
+ * perform_utility_analysis (analysis/utility_analysis.py, with
+ * analysis/cross_partition_combiners.py) folds the per-partition output into:
+ * one report per configuration over all partitions, and one per bucket of
+ * partition size.  Inputs are the device outputs of pdp_utility_analysis over
+ * all n_partitions codes (keep_probability NULL with PDP_UA_PUBLIC, metrics
+ * NULL without a metric), the same flags, and std_noise, a HOST array
+ * double[M][K] (copied to the workspace on `stream`; NULL without a metric).
+ *
+ * A partition takes part iff raw_statistics[p][0] > 0.  Its size is
+ * configuration 0's sum of the first metric (metrics[0][0][p][0]), or its
+ * privacy id count when there is no metric; its bucket is the largest of the
+ * PDP_UA_REPORT_BUCKETS lower bounds 0, 1, then 1, 2, 5 times 10^i (i = 1..12)
+ * that is <= the size (bucket 0 below 0).
+ *
+ * Per partition, configuration k and metric m, with s, cmin, cmax, el0, sl0
+ * the five metric fields, keep the selection probability (1 when public) and
+ * sn = std_noise[m][k], each line rounded operation by operation:
+ *   linf_drop = cmin - cmax;  l0_drop = -el0;
+ *   after = (s - l0_drop) - linf_drop;  sel_drop = after * (1 - keep);
+ *   bias = (el0 + cmin) + cmax;  l0_var = sl0 * sl0;  var = l0_var + sn * sn;
+ *   rmse = sqrt(bias * bias + var);
+ *   rmse_drop = keep * rmse + (1 - keep) * fabs(s);
+ *   abs[8] = {el0, l0_var, cmin, cmax, bias, var, rmse, rmse_drop}, each * keep;
+ *   rel[8] = abs / s (abs[1] and abs[5]: / (s * s)), all zero when s == 0.
+ *
+ * report: device double[PDP_UA_REPORT_BUCKETS + 1][F][K], F = 3 + 20 M, the
+ * last entry over all partitions.  Fields: 0 the total weight W = sum keep,
+ * 1 sum keep, 2 sum keep (1 - keep) (kept_partitions mean and variance); then
+ * per metric, at 3 + 20 m: sum_actual = sum s; the dropped sums l0, linf,
+ * partition_selection, each times (sum_actual == 0 ? 1 : 1 / sum_actual); the
+ * eight absolute and the eight relative errors (l0 mean, l0 var, linf_min,
+ * linf_max, mean, variance, rmse, rmse_with_dropped_partitions), each times
+ * (W == 0 ? 0 : 1 / W).  counts: device int64[PDP_UA_REPORT_BUCKETS + 1][2]:
+ * partitions taking part; with PDP_UA_PUBLIC those whose raw count
+ * (raw_statistics[p][1]) is not 0 in [0] and the empty ones in [1].
+ *
+ * Partition indices are sorted by bucket (stable), every bucket's run is
+ * summed in tiles, tiles in order, and the all-partitions entry adds the
+ * buckets' unscaled sums in bucket order: no floating-point atomic, two calls
+ * give the same bits.  The workspace (256-byte aligned) holds 5 B per
+ * partition and F K doubles per 128 partitions. */
+#define PDP_UA_REPORT_BUCKETS 38
+int pdp_utility_report_workspace_bytes(int64_t n_partitions, int32_t n_configurations, int32_t flags,
+                                       uint64_t* bytes);
+int pdp_utility_report(const int64_t* raw_statistics, const double* keep_probability, const double* metrics,
+                       int64_t n_partitions, int32_t n_configurations, int32_t flags, const double* std_noise,
+                       double* report, int64_t* counts, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* Multi-GPU sharding check (ColumnarBackend privacy_id_sharding="verify"):
  * counts the ids whose owner rank is not `rank`, where owner(id) =

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PIPELINEDP_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "lib", "libpipelinedp_amd.so")
 
 # constants (include/pipelinedp_amd.h)
-ABI_VERSION = 18
+ABI_VERSION = 19
 VALUE_NONE, VALUE_F64, VALUE_I64 = 0, 1, 2
 ACC_SUM, ACC_NSUM, ACC_NSUM2, SUM_PER_PARTITION, SUM_INT = 0x1, 0x2, 0x4, 0x8, 0x10
 DEBUG_CORRUPT_RECORDS = 0x40000000  # tests only (pipelinedp_amd.h)
@@ -42,6 +42,7 @@ VECTOR_SUM_SLOT = 0x56454353  # Philox slot of the vector-sum noise ("VECS")
 MAX_CONFIGURATIONS = 1024   # PDP_MAX_CONFIGURATIONS (utility analysis)
 UA_MAX_KEEP_TABLE = 1 << 20
 UA_SUM, UA_COUNT, UA_PRIVACY_ID_COUNT, UA_PUBLIC = 0x1, 0x2, 0x4, 0x8
+UA_REPORT_BUCKETS = 38      # PDP_UA_REPORT_BUCKETS (lower bounds of the report histogram)
 
 EXPORTED_SYMBOLS = (
     "pdp_abi_version",
@@ -75,6 +76,8 @@ EXPORTED_SYMBOLS = (
     "pdp_l0_impact_dropped",
     "pdp_utility_analysis_workspace_bytes",
     "pdp_utility_analysis",
+    "pdp_utility_report_workspace_bytes",
+    "pdp_utility_report",
     "pdp_bound_error_flags",
     "pdp_bound_error_flags_async",
     "pdp_owner_mismatches",
@@ -288,6 +291,8 @@ def signatures():
         "pdp_utility_analysis_workspace_bytes": (ctypes.c_int, [i64, i64, i32, i32, P(u64)]),
         "pdp_utility_analysis": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, P(UaConfigParams), i32, vp, P(i64), i32,
                                                 P(UaOutputs), vp, u64, vp]),
+        "pdp_utility_report_workspace_bytes": (ctypes.c_int, [i64, i32, i32, P(u64)]),
+        "pdp_utility_report": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, P(ctypes.c_double), vp, vp, vp, u64, vp]),
         "pdp_bound_error_flags": (ctypes.c_int, [vp, P(ctypes.c_uint32), vp]),
         "pdp_bound_error_flags_async": (ctypes.c_int, [vp, vp, vp]),
         "pdp_owner_mismatches": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),

@@ -175,6 +175,8 @@ class UtilityAnalysisResult:
         self.metrics = metric_arrays   # list (per metric) of {field: [P, K]}
         self.std_noise = std_noise     # [M][K]
         self.noise_kind = noise_kind   # [K]
+        self._raw_outputs = None       # run_utility_analysis's dict, [P]-indexed by partition code (analyze)
+        self._flags = 0
 
     @property
     def n_configurations(self):
@@ -265,9 +267,12 @@ class UtilityAnalysisEngine:
         metric_arrays = [{f: raw["metrics"][m, j].index_select(0, out_codes) for j, f in enumerate(FIELDS)}
                          for m in range(len(names))]
         keep = None if is_public else raw["keep_probability"].index_select(0, out_codes)
-        return UtilityAnalysisResult(keys, raw["raw_statistics"].index_select(0, out_codes), keep, names,
-                                     metric_arrays, [[p.std_noise[m] for p in plans] for m in range(len(names))],
-                                     [p.params.noise_kind for p in plans])
+        result = UtilityAnalysisResult(keys, raw["raw_statistics"].index_select(0, out_codes), keep, names,
+                                       metric_arrays, [[p.std_noise[m] for p in plans] for m in range(len(names))],
+                                       [p.params.noise_kind for p in plans])
+        # the kernel outputs over all partition codes, for utility_analysis.run_utility_report
+        result._raw_outputs, result._flags = raw, flags | (N.UA_PUBLIC if is_public else 0)
+        return result
 
 
 def _pair_columns(col, options, data_extractors, public_partitions, device):

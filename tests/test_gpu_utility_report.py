@@ -1,0 +1,202 @@
+"""The cross-partition stage of utility analysis on the GPU
+(pdp_utility_report, csrc/pdp_analysis_report.hip): fixture parity through
+perform_utility_analysis, the kernels' edge shapes against the NumPy
+restatement under the derived tolerances (tests/utility_report_util.py,
+DESIGN 3g), the selection-only case and bitwise reproducibility."""
+import numpy as np
+import pytest
+
+import pipelinedp_amd as pdp
+from pipelinedp_amd import _native as N
+from pipelinedp_amd import analysis
+from tests import utility_analysis_util as UA
+from tests import utility_report_util as R
+
+pytestmark = pytest.mark.gpu
+
+FIXTURE = R.load_fixture()
+TILE = 128  # kUrTile: partitions per reduce work item
+
+
+@pytest.mark.parametrize("case", FIXTURE, ids=[c["name"] for c in FIXTURE])
+def test_fixture_parity(case):
+    """Raw and pre-aggregated rows, public partitions (one of them empty) and
+    private ones with each selection strategy, both noise kinds, partition sizes
+    on the bucket edges: the reference's reports within the fixture bound, the
+    inputs' own bounds (3f) propagated."""
+    lib = UA.product_lib()
+    options, ext, col, public = UA.build_options(case, lib)
+    reports, result = analysis.perform_utility_analysis(col, pdp.ColumnarBackend(seed=1), options, ext, public)
+    assert isinstance(result, analysis.UtilityAnalysisResult) and len(reports) == options.n_configurations
+    keys, raw, keep, metrics, std_noise, noise_kind = R.arrays_of_expected(case)
+    assert sorted(result.partition_keys.tolist()) == keys
+    names = [m for m in UA.METRIC_ORDER if m in case["metrics"]]
+    for r in reports:
+        assert [str(mu.metric) for mu in r.metric_errors] == names
+        assert all(isinstance(b, analysis.UtilityReportBin) for b in r.utility_report_histogram)
+    slack = R.device_input_slack(case, keys, UA.product_plans(case))
+    _, bnds, _ = R.restate_report(raw, keep, metrics, std_noise, public is not None,
+                                  exact_actual=case["pre_aggregated"], fixture=True, slack=slack)
+    assert np.isfinite(bnds).all()
+    R.assert_records_close(case["name"], R.flatten_reports(reports), case["reports"], bnds)
+    # and, tighter, the restatement of the device's own per-partition arrays
+    _check_device(result._raw_outputs, result.std_noise, result._flags, exact_actual=case["pre_aggregated"])
+
+
+def _check_device(raw_outputs, std_noise, flags, exact_actual=True):
+    """pdp_utility_report on device arrays against their restatement."""
+    report, counts = analysis.run_utility_report(raw_outputs, std_noise, flags)
+    public = bool(flags & N.UA_PUBLIC)
+    host = {k: None if v is None else v.cpu().numpy() for k, v in raw_outputs.items()}
+    M = bin(flags & 7).count("1")
+    vals, bnds, want_counts = R.restate_report(host["raw_statistics"], host["keep_probability"],
+                                               host["metrics"] if M else None, std_noise, public,
+                                               exact_actual=exact_actual)
+    got, got_counts = report.cpu().numpy(), counts.cpu().numpy()
+    assert got.shape == vals.shape and (got_counts == want_counts).all(), (got_counts, want_counts)
+    assert np.isfinite(got).all() and np.isfinite(bnds).all()
+    diff = np.abs(got - vals)
+    worst = np.unravel_index(np.argmax(diff - bnds), diff.shape)
+    assert (diff <= bnds).all(), (worst, got[worst], vals[worst], diff[worst], bnds[worst])
+    return got, got_counts, vals
+
+
+def _inputs(sizes, K, M, public, seed=0, absent=(), keep=None, empty=()):
+    """Made-up kernel inputs: partition p has size sizes[p] (the first
+    metric's sum, the same for every configuration; the privacy id count when
+    M == 0); partitions in `absent` have privacy_id_count 0 and NaN everywhere
+    (they must not be read into any sum), those in `empty` raw count 0."""
+    import torch
+    rng = np.random.default_rng(seed)
+    P = len(sizes)
+    sizes = np.asarray(sizes, dtype=np.float64)
+    raw = np.stack([rng.integers(1, 50, P), rng.integers(1, 90, P)], axis=1).astype(np.int64)
+    if M == 0:
+        raw[:, 0] = sizes.astype(np.int64)
+    raw[list(empty), 1] = 0
+    metrics = np.zeros((M, 5, P, K))
+    for m in range(M):
+        # integer actual values: sum_actual is exact in every order
+        metrics[m, 0] = sizes[:, None] if m == 0 else rng.integers(-9, 40, (P, 1)).astype(np.float64)
+        metrics[m, 1] = np.where(rng.random((P, K)) < 0.5, 0.0, rng.random((P, K)))
+        metrics[m, 2] = np.where(rng.random((P, K)) < 0.5, 0.0, -3 * rng.random((P, K)))
+        metrics[m, 3] = -np.abs(metrics[m, 0]) * rng.random((P, K))
+        metrics[m, 4] = 2 * rng.random((P, K))
+    kp = None if public else (rng.random((P, K)) if keep is None else np.full((P, K), float(keep)))
+    if len(absent):
+        raw[list(absent)] = [0, 7]
+        metrics[:, :, list(absent), :] = np.nan
+        if kp is not None:
+            kp[list(absent)] = np.nan
+    std_noise = [[float(v) for v in 0.5 + rng.random(K)] for _ in range(M)]
+    flags = (N.UA_SUM, N.UA_SUM | N.UA_COUNT, 7)[M - 1] if M else 0
+    dev = torch.device("cuda:0")
+    out = dict(raw_statistics=torch.as_tensor(raw, device=dev),
+               keep_probability=None if public else torch.as_tensor(kp, device=dev),
+               metrics=torch.as_tensor(metrics, device=dev))
+    return out, std_noise, flags | (N.UA_PUBLIC if public else 0)
+
+
+def _mixed_sizes(P, seed):
+    """Sizes over a few buckets: negatives, 0 (relative terms zero), bucket edges."""
+    rng = np.random.default_rng(seed)
+    return rng.choice([-4.0, 0.0, 0.0, 1.0, 3.0, 9.0, 10.0, 19.0, 20.0, 49.0, 50.0, 1e6, 5e12, 1e13], P)
+
+
+SHAPES = [
+    # (sizes, K, M, public): P = 1; a bucket of exactly one tile, one more, three tiles plus one (all in one bucket)
+    ([7.0], 1, 1, False),
+    ([30.0] * TILE, 64, 1, False),
+    ([30.0] * (TILE + 1), 65, 2, False),
+    ([30.0] * (3 * TILE + 1), 63, 3, True),
+    # every bucket: each lower bound, and a value inside the bucket
+    ([float(b) for b in R.BOUNDS] + [float(b) * 1.5 + 0.5 for b in R.BOUNDS], 130, 1, False),
+    ([float(b) for b in R.BOUNDS] * 2, 3, 2, True),
+    (list(_mixed_sizes(2 * TILE + 37, 1)), 64, 3, False),
+    (list(_mixed_sizes(300, 2)), 5, 1, True),
+    (list(_mixed_sizes(9, 3)), 1024, 1, False),
+    (list(_mixed_sizes(5, 4)), 1024, 3, True),
+]
+
+
+@pytest.mark.parametrize("shape", range(len(SHAPES)))
+def test_kernel_edges_against_restatement(shape):
+    """Tiles (one, one more, three and one), every bucket, K below, at and above
+    a wave, 0 to 3 metrics, public and private; every fourth partition has
+    privacy_id_count 0 and NaN data, every fifth public one raw count 0."""
+    sizes, K, M, public = SHAPES[shape]
+    P = len(sizes)
+    absent = [] if P < 4 or shape in (1, 2, 3) else list(range(1, P, 4))
+    empty = list(range(0, P, 5)) if public else []
+    got, counts, _ = _check_device(*_inputs(sizes, K, M, public, seed=shape, absent=absent, empty=empty))
+    assert counts[38].sum() == P - len(absent)
+    if public:
+        assert counts[38, 1] == len(set(empty) - set(absent)) > 0
+    if shape in (1, 2, 3):
+        assert (np.nonzero(counts[:38].sum(axis=1))[0] == [3]).all()  # 30 lies in [20, 50)
+    if shape in (4, 5):
+        assert (counts[:38].sum(axis=1) > 0).all()
+
+
+def test_absent_partitions_between_tiles():
+    """Partitions without a privacy id interleaved with a bucket of a tile and one."""
+    sizes = [30.0] * (2 * TILE + 2)
+    absent = list(range(0, len(sizes), 2))
+    _, counts, _ = _check_device(*_inputs(sizes, 65, 2, False, seed=11, absent=absent))
+    assert counts[3, 0] == counts[38, 0] == TILE + 1 and counts[:, 1].sum() == 0
+
+
+def test_total_weight_zero_gives_zeros():
+    """Every keep probability 0: W = 0, the averaged fields are 0.0, not NaN."""
+    got, counts, _ = _check_device(*_inputs(list(_mixed_sizes(40, 5)), 3, 2, False, seed=5, keep=0.0))
+    for m in range(2):
+        assert (got[:, 3 + 20 * m + 4:3 + 20 * (m + 1)] == 0.0).all()
+    assert (got[:, :3] == 0.0).all() and counts[38, 0] == 40
+    assert (got[38, 3 + 1:3 + 4] != 0.0).any()  # the dropped ratios do not depend on W
+
+
+def test_sum_actual_zero_scales_dropped_by_one():
+    """+3 and -3 (and 0): sum_actual == 0 with non-zero partitions; the dropped
+    sums are then reported unscaled.  Negative sums: negative relative RMSE."""
+    inputs = _inputs([3.0, -3.0, 0.0, -3.0, 3.0], 2, 1, False, seed=6)
+    got, _, vals = _check_device(*inputs)
+    m = inputs[0]["metrics"].cpu().numpy()[0]
+    assert (got[38, 3] == 0.0).all() and (got[0, 3] == -6.0).all()
+    assert np.allclose(got[38, 3 + 1], -m[3].sum(axis=0), rtol=1e-12)      # l0 dropped, times 1
+    assert np.allclose(got[0, 3 + 1], -m[3][[1, 2, 3]].sum(axis=0) / -6.0, rtol=1e-12)
+    assert (got[0, 3 + 12 + 6] < 0).all() and (got[1, 3 + 12 + 6] > 0).all()  # relative rmse by bucket
+
+
+def test_selection_only():
+    """Private partitions, no metric: buckets by privacy_id_count, against the
+    restatement; through perform_utility_analysis metric_errors is None."""
+    got, counts, _ = _check_device(*_inputs([1, 9, 10, 19, 20, 20, 300, 1], 65, 0, False, seed=7, absent=[3]))
+    assert got.shape == (39, 3, 65)
+    assert [int(c) for c in counts[:7, 0]] == [0, 3, 1, 2, 0, 0, 1] and counts[38, 0] == 7
+    rows = [(pid, pk, 1.0) for pk, n in enumerate([1, 12, 25]) for pid in range(n)]
+    params = pdp.AggregateParams(metrics=[], noise_kind=pdp.NoiseKind.LAPLACE, max_partitions_contributed=2,
+                                 max_contributions_per_partition=1)
+    options = analysis.UtilityAnalysisOptions(1.0, 1e-5, params, analysis.MultiParameterConfiguration(
+        max_partitions_contributed=[1, 3]))
+    ext = pdp.DataExtractors(privacy_id_extractor=lambda r: r[0], partition_extractor=lambda r: r[1],
+                             value_extractor=lambda r: r[2])
+    reports, result = analysis.perform_utility_analysis(rows, pdp.ColumnarBackend(), options, ext)
+    keep = result.keep_probability.cpu().numpy()
+    order = np.argsort(result.partition_keys)
+    for k, r in enumerate(reports):
+        assert r.metric_errors is None and r.configuration_index == k
+        assert r.partitions_info.num_dataset_partitions == 3
+        assert r.partitions_info.strategy == pdp.PartitionSelectionStrategy.TRUNCATED_GEOMETRIC
+        assert [(b.partition_size_from, b.partition_size_to) for b in r.utility_report_histogram] == \
+            [(1, 10), (10, 20), (20, 50)]
+        for b, p in zip(r.utility_report_histogram, order):
+            assert b.report.partitions_info.kept_partitions.mean == keep[p, k]
+            assert b.report.partitions_info.kept_partitions.var == keep[p, k] * (1 - keep[p, k])
+        assert abs(r.partitions_info.kept_partitions.mean - keep[:, k].sum()) <= 3 * R.U * keep[:, k].sum()
+
+
+def test_two_calls_are_bitwise_equal():
+    import torch
+    inputs = _inputs(list(_mixed_sizes(3 * TILE + 5, 8)), 130, 3, False, seed=8, absent=[2, 77])
+    a, b = analysis.run_utility_report(*inputs), analysis.run_utility_report(*inputs)
+    assert torch.equal(a[0].view(torch.int64), b[0].view(torch.int64)) and torch.equal(a[1], b[1])
