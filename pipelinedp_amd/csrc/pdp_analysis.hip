@@ -6,23 +6,16 @@
 //                  the key P and sets the error word), row indices, and
 //                  RawStatistics by integer atomics
 //   k_ua_hist / k_ua_scatter
-//                  a stable LSD radix sort of (key, row index) by 8-bit digits:
-//                  per-tile digit counts, one device scan (scan_u32) of the
-//                  digit-major count table, then a scatter that ranks equal
-//                  digits in row order (wave ballots, then waves in order), so
-//                  the sorted order is the same in every run
+//                  a stable LSD radix sort of (key, row index) by 8-bit digits,
+//                  one stable tile sort pass (pdp_segments.h) per digit
 //   k_ua_offsets   segment offsets off[p] = lower_bound(sorted keys, p)
 //   k_ua_gather    pair fields in sorted order (count, sum, n_partitions)
-//   k_ua_reduce    lanes across configurations: lane k of a wave keeps
+//   k_ua_reduce / k_ua_combine
+//                  the segment reduce of pdp_segments.h with tiles of kUaChunk
+//                  pairs and lanes across configurations: lane k of a wave keeps
 //                  (l0, linf, min_sum, max_sum) of configuration k in registers
-//                  and walks a segment whose pair fields are loaded 64 at a
-//                  time and broadcast; fp64 accumulators per lane.  Work items:
-//                  every partition of <= kUaChunk pairs (whole), and every tile
-//                  of kUaChunk consecutive sorted pairs, which sums the pieces
-//                  of the (at most two) longer partitions it overlaps into
-//                  partial[tile][0 | 1]
-//   k_ua_combine   one wave per longer partition adds its tiles' partials in
-//                  tile order
+//                  and walks a piece whose pair fields are loaded 64 at a time
+//                  and broadcast; fp64 accumulators per lane
 //   k_ua_select    one wave per (partition, configuration): the exact
 //                  Poisson-binomial PMF for n <= 100 pairs (entry i in lane
 //                  i % 64), the refined normal approximation from the moments
@@ -30,7 +23,7 @@
 // No floating-point atomic, and every order of summation is fixed: two runs
 // give the same bits.  Every product and sum is rounded on its own (no fused
 // multiply-add), so a term equals the reference's NumPy expression bit for bit.
-#include "pdp_internal.h"
+#include "pdp_segments.h"
 
 #pragma clang fp contract(off)
 
@@ -46,18 +39,14 @@ struct UWs {
   uint64_t err, params, koff, key0, key1, idx0, idx1, hist, chunks, off, scnt, ssum, snp, mom, partial, total;
 };
 
-inline int ua_n_metrics(int flags) {
-  return ((flags & PDP_UA_SUM) ? 1 : 0) + ((flags & PDP_UA_COUNT) ? 1 : 0) + ((flags & PDP_UA_PRIVACY_ID_COUNT) ? 1 : 0);
-}
 inline bool ua_private(int flags) { return (flags & PDP_UA_PUBLIC) == 0; }
 inline int ua_fields(int flags) { return 5 * ua_n_metrics(flags) + (ua_private(flags) ? kUaMoments : 0); }
-inline int64_t ua_sort_tiles(int64_t n) { return n > 0 ? (n + kUaTile - 1) / kUaTile : 1; }
-__host__ __device__ inline int64_t ua_chunks(int64_t n) { return (n + kUaChunk - 1) / kUaChunk; }
+inline int64_t ua_chunks(int64_t n) { return seg_tiles<kUaChunk>(n); }
 
 UWs ulayout(int64_t n_pairs, int64_t P, int K, int flags) {
   UWs w{};
   const uint64_t n = (uint64_t)(n_pairs > 0 ? n_pairs : 1);
-  const uint64_t hist_len = 256 * (uint64_t)ua_sort_tiles(n_pairs);
+  const uint64_t hist_len = 256 * (uint64_t)seg_tiles<kUaTile>((int64_t)n);
   uint64_t off = 0;
   w.err = off; off = align256(off + 16);
   w.params = off; off = align256(off + (uint64_t)K * sizeof(pdp_ua_config_params));
@@ -98,68 +87,16 @@ __global__ void __launch_bounds__(kBlock) k_ua_init(int64_t n, int64_t P, const 
   }
 }
 
-// hist[digit * n_tiles + tile] = records of the tile with that digit
-__global__ void __launch_bounds__(kBlock) k_ua_hist(int64_t n, int shift, const unsigned* __restrict__ key,
-                                                    unsigned* hist, int64_t n_tiles) {
-  __shared__ unsigned h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kUaTile;
-  for (int r = 0; r < kUaTile / kBlock; ++r) {
-    const int64_t i = base + r * kBlock + threadIdx.x;
-    if (i < n) atomicAdd(&h[(key[i] >> shift) & 255u], 1u);
+// what the stable LSD radix sort (8-bit digits, pdp_segments.h) moves: the key and the row index
+struct UaEmit {
+  const unsigned* idx_in;
+  unsigned *key_out, *idx_out;
+  __device__ void operator()(int64_t i, unsigned k, unsigned pos) const {
+    const unsigned row = idx_in[i];  // read before the first store: the two may alias for all the compiler knows
+    key_out[pos] = k;
+    idx_out[pos] = row;
   }
-  __syncthreads();
-  hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// Stable: within a tile the records go out in rounds of kBlock consecutive
-// records; in a round a record's rank among equal digits is the number of
-// such records in earlier waves plus those in lower lanes of its own wave.
-__global__ void __launch_bounds__(kBlock) k_ua_scatter(int64_t n, int shift, const unsigned* __restrict__ key_in,
-                                                       const unsigned* __restrict__ idx_in, unsigned* key_out,
-                                                       unsigned* idx_out, const unsigned* __restrict__ hist,
-                                                       int64_t n_tiles) {
-  constexpr int kWaves = kBlock / 64;
-  __shared__ unsigned base[256];
-  __shared__ unsigned cnt[kWaves][256];
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  base[threadIdx.x] = hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x];
-  for (int w = 0; w < kWaves; ++w) cnt[w][threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t tile0 = (int64_t)blockIdx.x * kUaTile;
-  for (int r = 0; r < kUaTile / kBlock; ++r) {
-    const int64_t i = tile0 + r * kBlock + threadIdx.x;
-    const bool valid = i < n;
-    const unsigned k = valid ? key_in[i] : 0u;
-    const unsigned d = (k >> shift) & 255u;
-    unsigned long long same = __ballot(valid);
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(valid && bit);
-      same &= bit ? bal : ~bal;
-    }
-    const unsigned below = (unsigned)__popcll(same & ((1ULL << lane) - 1ULL));
-    if (valid && below == 0) cnt[wave][d] = (unsigned)__popcll(same);
-    __syncthreads();
-    if (valid) {
-      unsigned pos = base[d] + below;
-      for (int w = 0; w < wave; ++w) pos += cnt[w][d];
-      if ((int64_t)pos < n) {
-        key_out[pos] = k;
-        idx_out[pos] = idx_in[i];
-      }
-    }
-    __syncthreads();
-    unsigned add = 0;
-    for (int w = 0; w < kWaves; ++w) {
-      add += cnt[w][threadIdx.x];
-      cnt[w][threadIdx.x] = 0;
-    }
-    base[threadIdx.x] += add;
-    __syncthreads();
-  }
-}
+};
 
 // off[p] = first sorted position whose key is >= p, p in [0, P]
 __global__ void __launch_bounds__(kBlock) k_ua_offsets(int64_t n, int64_t P, const unsigned* __restrict__ key,
@@ -193,14 +130,6 @@ __global__ void __launch_bounds__(kBlock) k_ua_gather(int64_t n, int64_t P, cons
 }
 
 // ---------------------------------------------------------------- reduce --
-// value of lane `j` (wave-uniform) for every lane
-__device__ __forceinline__ double ua_bcast(double v, int j) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(unsigned)(unsigned long long)b, j);
-  const int hi = __builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), j);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-
 // q = min(1, l0 / n_partitions), 0 for n_partitions <= 0 (np.where(n > 0, np.minimum(1, l0 / n), 0))
 __device__ __forceinline__ double ua_q(double l0, double np) { return np > 0.0 ? fmin(1.0, l0 / np) : 0.0; }
 
@@ -242,7 +171,7 @@ __device__ __forceinline__ void ua_piece(UaAcc<M, SEL>& acc, const UaLane& c, co
       np_l = (double)snp[r0 + lane];
     }
     for (int j = 0; j < m; ++j) {
-      const double cnt = ua_bcast(cnt_l, j), sm = ua_bcast(sum_l, j), np = ua_bcast(np_l, j);
+      const double cnt = bcast_f64(cnt_l, j), sm = bcast_f64(sum_l, j), np = bcast_f64(np_l, j);
       const double q = ua_q(c.l0, np), omq = 1.0 - q;
       int s = 0;
       if constexpr ((M & 1) != 0) {
@@ -291,16 +220,6 @@ __device__ __forceinline__ void ua_write(const UaAcc<M, SEL>& acc, const UaOut& 
   }
 }
 
-// partition holding sorted position r: the p with off[p] <= r < off[p + 1] (r < off[P])
-__device__ __forceinline__ int64_t ua_partition_of(const unsigned* __restrict__ off, int64_t P, uint64_t r) {
-  int64_t lo = 0, hi = P;  // smallest q in [1, P] with off[q] > r
-  while (lo + 1 < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((uint64_t)off[mid] > r) hi = mid; else lo = mid;
-  }
-  return hi - 1;
-}
-
 template <int M, bool SEL>
 __global__ void __launch_bounds__(kBlock) k_ua_reduce(int64_t n, int64_t P, int K,
                                                       const pdp_ua_config_params* __restrict__ params,
@@ -309,7 +228,7 @@ __global__ void __launch_bounds__(kBlock) k_ua_reduce(int64_t n, int64_t P, int 
                                                       const double* __restrict__ ssum,
                                                       const long long* __restrict__ snp, UaOut o, double* partial) {
   constexpr int kF = UaAcc<M, SEL>::kF;
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63);
   const int k = (int)blockIdx.y * 64 + lane;
   const bool active = k < K;
   UaLane c{1.0, 0.0, 0.0, 0.0};
@@ -320,66 +239,41 @@ __global__ void __launch_bounds__(kBlock) k_ua_reduce(int64_t n, int64_t P, int 
     c.hi = params[k].max_sum;
   }
   const uint64_t total = off[P] < (uint64_t)n ? off[P] : (uint64_t)n;
-  const int64_t tiles = ua_chunks(n), items = P + tiles;
-  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
   UaAcc<M, SEL> acc;
-  for (int64_t it = (int64_t)blockIdx.x * (kBlock / 64) + wave; it < items; it += wstride) {
-    if (it < P) {  // a partition of at most kUaChunk pairs, whole (an empty one: zeros)
-      const uint64_t a = off[it], b = off[it + 1];
-      if (b < a || b - a > kUaChunk || b > total) continue;
-      ua_piece<M, SEL>(acc, c, scnt, ssum, snp, a, b, lane);
-      if (active) ua_write<M, SEL>(acc, o, P, K, it, k);
-      continue;
-    }
-    const uint64_t tile = (uint64_t)(it - P);
-    const uint64_t r0 = tile * kUaChunk;
-    if (r0 >= total) continue;
-    const uint64_t r1 = r0 + kUaChunk < total ? r0 + kUaChunk : total;
-    const int64_t pf = ua_partition_of(off, P, r0), pl = ua_partition_of(off, P, r1 - 1);
-    if (off[pf + 1] - off[pf] > kUaChunk) {
-      const uint64_t e = off[pf + 1] < r1 ? off[pf + 1] : r1;
-      ua_piece<M, SEL>(acc, c, scnt, ssum, snp, r0, e, lane);
-      if (active) {
+  // an empty partition is a piece: zeros
+  seg_for_each_piece<kUaChunk, true>(off, P, n, total, [&](uint64_t a, uint64_t b, SegDst dst) {
+    ua_piece<M, SEL>(acc, c, scnt, ssum, snp, a, b, lane);
+    if (!active) return;
+    if (dst.whole) {
+      ua_write<M, SEL>(acc, o, P, K, (int64_t)dst.at, k);
+    } else {
 #pragma unroll
-        for (int f = 0; f < kF; ++f) partial[((tile * 2) * kF + f) * (uint64_t)K + k] = acc.f[f];
-      }
+      for (int f = 0; f < kF; ++f) partial[(dst.at * kF + f) * (uint64_t)K + k] = acc.f[f];
     }
-    if (pl != pf && off[pl + 1] - off[pl] > kUaChunk) {
-      ua_piece<M, SEL>(acc, c, scnt, ssum, snp, off[pl], r1, lane);
-      if (active) {
-#pragma unroll
-        for (int f = 0; f < kF; ++f) partial[((tile * 2 + 1) * kF + f) * (uint64_t)K + k] = acc.f[f];
-      }
-    }
-  }
+  });
 }
 
-// partitions of more than kUaChunk pairs: tile t holds the partition's piece in
-// partial[t][0] if the partition owns the tile's first position, else in
-// partial[t][1] (only its first tile can); added in tile order
+// partitions of more than kUaChunk pairs: their tiles' partials, added in tile order
 template <int M, bool SEL>
 __global__ void __launch_bounds__(kBlock) k_ua_combine(int64_t n, int64_t P, int K, const unsigned* __restrict__ off,
                                                        const double* __restrict__ partial, UaOut o) {
   constexpr int kF = UaAcc<M, SEL>::kF;
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63);
   const int k = (int)blockIdx.y * 64 + lane;
   const bool active = k < K;
   const uint64_t total = off[P] < (uint64_t)n ? off[P] : (uint64_t)n;
-  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t p = (int64_t)blockIdx.x * (kBlock / 64) + wave; p < P; p += wstride) {
-    const uint64_t a = off[p], b = off[p + 1];
-    if (b <= a || b - a <= kUaChunk || b > total || !active) continue;
-    const uint64_t t0 = a / kUaChunk, t1 = (b - 1) / kUaChunk;
+  seg_for_each_long<kUaChunk>(off, P, total, [&](int64_t p, uint64_t t0, uint64_t t1, bool first_in_slot_1) {
+    if (!active) return;
     UaAcc<M, SEL> acc;
 #pragma unroll
     for (int f = 0; f < kF; ++f) acc.f[f] = 0.0;
     for (uint64_t t = t0; t <= t1; ++t) {
-      const uint64_t slot = (t == t0 && a != t0 * kUaChunk) ? 1 : 0;
+      const uint64_t slot = (t == t0 && first_in_slot_1) ? 1 : 0;
 #pragma unroll
       for (int f = 0; f < kF; ++f) acc.f[f] += partial[((t * 2 + slot) * kF + f) * (uint64_t)K + k];
     }
     ua_write<M, SEL>(acc, o, P, K, p, k);
-  }
+  });
 }
 
 template <int M, bool SEL>
@@ -452,10 +346,10 @@ __global__ void __launch_bounds__(kBlock) k_ua_select(int64_t n, int64_t P, int 
       const double q1 = lane + 64 < m ? ua_q(l0, (double)snp[a + 64 + lane]) : 0.0;
       double A = lane == 0 ? 1.0 : 0.0, B = 0.0;
       for (int j = 0; j < m; ++j) {
-        const double pr = j < 64 ? ua_bcast(q0, j) : ua_bcast(q1, j - 64);
+        const double pr = j < 64 ? bcast_f64(q0, j) : bcast_f64(q1, j - 64);
         const double omp = 1.0 - pr;
         double upA = __shfl_up(A, 1, 64), upB = __shfl_up(B, 1, 64);
-        const double a63 = ua_bcast(A, 63);
+        const double a63 = bcast_f64(A, 63);
         if (lane == 0) {
           upA = 0.0;
           upB = a63;
@@ -491,19 +385,10 @@ __global__ void __launch_bounds__(kBlock) k_ua_select(int64_t n, int64_t P, int 
   }
 }
 
-int ua_check_shape(int64_t n_pairs, int64_t n_partitions, int32_t K, int32_t flags) {
+int ua_check_pairs(int64_t n_pairs, int64_t n_partitions, int32_t K, int32_t flags) {
   if (n_pairs < 0) return set_error(PDP_E_INVALID, "n_pairs < 0");
   if (n_pairs >= ((int64_t)1 << 31)) return set_error(PDP_E_UNSUPPORTED, "n_pairs must be < 2^31");
-  if (n_partitions < 1) return set_error(PDP_E_INVALID, "n_partitions must be >= 1");
-  if (n_partitions >= ((int64_t)1 << 31)) return set_error(PDP_E_UNSUPPORTED, "n_partitions must be < 2^31");
-  if (K < 1) return set_error(PDP_E_INVALID, "n_configurations must be >= 1");
-  if (K > PDP_MAX_CONFIGURATIONS)
-    return set_error(PDP_E_UNSUPPORTED, "n_configurations above PDP_MAX_CONFIGURATIONS");
-  if (flags & ~(PDP_UA_SUM | PDP_UA_COUNT | PDP_UA_PRIVACY_ID_COUNT | PDP_UA_PUBLIC))
-    return set_error(PDP_E_INVALID, "unknown utility analysis flags");
-  if ((flags & PDP_UA_PUBLIC) && ua_n_metrics(flags) == 0)
-    return set_error(PDP_E_INVALID, "public partitions without a metric: nothing to analyse");
-  return PDP_OK;
+  return ua_check_shape(n_partitions, K, flags);
 }
 
 }  // namespace
@@ -515,7 +400,7 @@ extern "C" {
 
 int pdp_utility_analysis_workspace_bytes(int64_t n_pairs, int64_t n_partitions, int32_t n_configurations,
                                          int32_t flags, uint64_t* bytes) {
-  const int rc = ua_check_shape(n_pairs, n_partitions, n_configurations, flags);
+  const int rc = ua_check_pairs(n_pairs, n_partitions, n_configurations, flags);
   if (rc != PDP_OK) return rc;
   if (bytes == nullptr) return set_error(PDP_E_INVALID, "bytes is NULL");
   *bytes = ulayout(n_pairs, n_partitions, n_configurations, flags).total;
@@ -527,7 +412,7 @@ int pdp_utility_analysis(const int64_t* partition, const int64_t* count, const d
                          const pdp_ua_config_params* params, int32_t n_configurations, const double* keep_tables,
                          const int64_t* keep_offsets, int32_t flags, const pdp_ua_outputs* out, void* workspace,
                          uint64_t workspace_bytes, void* stream) {
-  int rc = ua_check_shape(n_pairs, n_partitions, n_configurations, flags);
+  int rc = ua_check_pairs(n_pairs, n_partitions, n_configurations, flags);
   if (rc != PDP_OK) return rc;
   const int K = n_configurations;
   const int64_t n = n_pairs, P = n_partitions;
@@ -588,16 +473,11 @@ int pdp_utility_analysis(const int64_t* partition, const int64_t* count, const d
     rc = launch("k_ua_init", k_ua_init, dim3(grid_for(n)), dim3(kBlock), 0, st, n, P, partition, count, key[0], idx[0],
                 (long long*)out->raw_statistics, err);
     if (rc != PDP_OK) return rc;
-    const int64_t n_tiles = ua_sort_tiles(n);
     const int key_bits = bits_for(P + 1);
     for (int shift = 0; shift < key_bits; shift += 8) {
-      rc = launch("k_ua_hist", k_ua_hist, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, n, shift, key[cur], hist,
-                  n_tiles);
-      if (rc != PDP_OK) return rc;
-      rc = scan_u32(hist, 256 * n_tiles, (unsigned*)(ws + w.chunks), st);
-      if (rc != PDP_OK) return rc;
-      rc = launch("k_ua_scatter", k_ua_scatter, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, n, shift, key[cur],
-                  idx[cur], key[cur ^ 1], idx[cur ^ 1], hist, n_tiles);
+      rc = tile_sort_pass<8, kUaTile>("k_ua_hist", "k_ua_scatter", n, 256, shift, key[cur],
+                                      UaEmit{idx[cur], key[cur ^ 1], idx[cur ^ 1]}, hist,
+                                      (unsigned*)(ws + w.chunks), st);
       if (rc != PDP_OK) return rc;
       cur ^= 1;
     }

@@ -9,11 +9,9 @@
 //                  (raw_statistics[p][0] <= 0); the integer counts per bucket
 //                  by integer atomics
 //   k_ur_hist / k_ur_scatter
-//                  one stable counting-sort pass of the partition indices by
-//                  key (39 keys): per-tile key counts, one device scan
-//                  (scan_u32) of the key-major count table, then a scatter that
-//                  ranks equal keys in index order (wave ballots, then waves in
-//                  order), so a bucket's run holds its partitions ascending
+//                  one stable tile sort pass (pdp_segments.h) of the partition
+//                  indices by key (39 keys), so a bucket's run holds its
+//                  partitions ascending
 //   k_ur_reduce    lanes across configurations: one wave per (tile of kUrTile
 //                  partitions of one bucket's run, metric, chunk of 64
 //                  configurations) forms the per-partition terms and keeps 20
@@ -26,7 +24,7 @@
 // No floating-point atomic, and every order of summation is fixed: two runs
 // give the same bits.  Every product, sum, quotient and root is rounded on its
 // own (no fused multiply-add), so a term equals its NumPy expression bit for bit.
-#include "pdp_internal.h"
+#include "pdp_segments.h"
 
 #pragma clang fp contract(off)
 
@@ -53,17 +51,14 @@ struct RWs {
   uint64_t sn, key, order, hist, chunks, partial, sums, total;
 };
 
-inline int ur_n_metrics(int flags) {
-  return ((flags & PDP_UA_SUM) ? 1 : 0) + ((flags & PDP_UA_COUNT) ? 1 : 0) + ((flags & PDP_UA_PRIVACY_ID_COUNT) ? 1 : 0);
-}
 inline int ur_fields(int M) { return kUrSel + kUrPerMetric * M; }
-inline int64_t ur_sort_tiles(int64_t P) { return (P + kUrSortTile - 1) / kUrSortTile; }
+inline int64_t ur_sort_tiles(int64_t P) { return seg_tiles<kUrSortTile>(P); }
 // the buckets' runs are tiled one by one: at most one ragged tile per bucket
 inline int64_t ur_max_tiles(int64_t P) { return P / kUrTile + kUrBuckets; }
 
 RWs rlayout(int64_t P, int K, int flags) {
   RWs w{};
-  const int M = ur_n_metrics(flags);
+  const int M = ua_n_metrics(flags);
   const uint64_t hist_len = (uint64_t)kUrKeys * (uint64_t)ur_sort_tiles(P);
   const uint64_t FK = (uint64_t)ur_fields(M) * (uint64_t)K * 8;
   uint64_t off = 0;
@@ -111,65 +106,11 @@ __global__ void __launch_bounds__(kBlock) k_ur_keys(int64_t P, int K, const long
   }
 }
 
-// hist[key * n_tiles + tile] = partitions of the tile with that key
-__global__ void __launch_bounds__(kBlock) k_ur_hist(int64_t P, const unsigned char* __restrict__ key, unsigned* hist,
-                                                    int64_t n_tiles) {
-  __shared__ unsigned h[64];
-  if (threadIdx.x < 64) h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kUrSortTile;
-  for (int r = 0; r < kUrSortTile / kBlock; ++r) {
-    const int64_t i = base + r * kBlock + threadIdx.x;
-    if (i < P) atomicAdd(&h[key[i] & 63u], 1u);
-  }
-  __syncthreads();
-  if (threadIdx.x < kUrKeys) hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// Stable: within a tile the partitions go out in rounds of kBlock consecutive
-// indices; in a round an index's rank among equal keys is the number of such
-// indices in earlier waves plus those in lower lanes of its own wave.
-__global__ void __launch_bounds__(kBlock) k_ur_scatter(int64_t P, const unsigned char* __restrict__ key,
-                                                       unsigned* order, const unsigned* __restrict__ hist,
-                                                       int64_t n_tiles) {
-  constexpr int kWaves = kBlock / 64;
-  __shared__ unsigned base[64];
-  __shared__ unsigned cnt[kWaves][64];
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  if (threadIdx.x < 64) base[threadIdx.x] = threadIdx.x < kUrKeys ? hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] : 0u;
-  cnt[wave][lane] = 0;
-  __syncthreads();
-  const int64_t tile0 = (int64_t)blockIdx.x * kUrSortTile;
-  for (int r = 0; r < kUrSortTile / kBlock; ++r) {
-    const int64_t i = tile0 + r * kBlock + threadIdx.x;
-    const bool valid = i < P;
-    const unsigned d = valid ? (key[i] & 63u) : 0u;
-    unsigned long long same = __ballot(valid);
-    for (int b = 0; b < 6; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(valid && bit);
-      same &= bit ? bal : ~bal;
-    }
-    const unsigned below = (unsigned)__popcll(same & ((1ULL << lane) - 1ULL));
-    if (valid && below == 0) cnt[wave][d] = (unsigned)__popcll(same);
-    __syncthreads();
-    if (valid) {
-      unsigned pos = base[d] + below;
-      for (int w = 0; w < wave; ++w) pos += cnt[w][d];
-      if ((int64_t)pos < P) order[pos] = (unsigned)i;
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      unsigned add = 0;
-      for (int w = 0; w < kWaves; ++w) {
-        add += cnt[w][threadIdx.x];
-        cnt[w][threadIdx.x] = 0;
-      }
-      base[threadIdx.x] += add;
-    }
-    __syncthreads();
-  }
-}
+// the counting sort's digit is the key; only the partition's index moves
+struct UrEmit {
+  unsigned* order;
+  __device__ void operator()(int64_t i, unsigned, unsigned pos) const { order[pos] = (unsigned)i; }
+};
 
 // ---------------------------------------------------------------- reduce --
 // After the scan hist[key * n_tiles] is the first sorted position of `key`.
@@ -348,19 +289,6 @@ __global__ void __launch_bounds__(kBlock) k_ur_final(int K, int F, const double*
   }
 }
 
-int ur_check_shape(int64_t n_partitions, int32_t K, int32_t flags) {
-  if (n_partitions < 1) return set_error(PDP_E_INVALID, "n_partitions must be >= 1");
-  if (n_partitions >= ((int64_t)1 << 31)) return set_error(PDP_E_UNSUPPORTED, "n_partitions must be < 2^31");
-  if (K < 1) return set_error(PDP_E_INVALID, "n_configurations must be >= 1");
-  if (K > PDP_MAX_CONFIGURATIONS)
-    return set_error(PDP_E_UNSUPPORTED, "n_configurations above PDP_MAX_CONFIGURATIONS");
-  if (flags & ~(PDP_UA_SUM | PDP_UA_COUNT | PDP_UA_PRIVACY_ID_COUNT | PDP_UA_PUBLIC))
-    return set_error(PDP_E_INVALID, "unknown utility analysis flags");
-  if ((flags & PDP_UA_PUBLIC) && ur_n_metrics(flags) == 0)
-    return set_error(PDP_E_INVALID, "public partitions without a metric: nothing to analyse");
-  return PDP_OK;
-}
-
 }  // namespace
 }  // namespace pdp
 
@@ -370,7 +298,7 @@ extern "C" {
 
 int pdp_utility_report_workspace_bytes(int64_t n_partitions, int32_t n_configurations, int32_t flags,
                                        uint64_t* bytes) {
-  const int rc = ur_check_shape(n_partitions, n_configurations, flags);
+  const int rc = ua_check_shape(n_partitions, n_configurations, flags);
   if (rc != PDP_OK) return rc;
   if (bytes == nullptr) return set_error(PDP_E_INVALID, "bytes is NULL");
   *bytes = rlayout(n_partitions, n_configurations, flags).total;
@@ -380,12 +308,12 @@ int pdp_utility_report_workspace_bytes(int64_t n_partitions, int32_t n_configura
 int pdp_utility_report(const int64_t* raw_statistics, const double* keep_probability, const double* metrics,
                        int64_t n_partitions, int32_t n_configurations, int32_t flags, const double* std_noise,
                        double* report, int64_t* counts, void* workspace, uint64_t workspace_bytes, void* stream) {
-  int rc = ur_check_shape(n_partitions, n_configurations, flags);
+  int rc = ua_check_shape(n_partitions, n_configurations, flags);
   if (rc != PDP_OK) return rc;
   const int K = n_configurations;
   const int64_t P = n_partitions;
   const bool is_public = (flags & PDP_UA_PUBLIC) != 0;
-  const int M = ur_n_metrics(flags), F = ur_fields(M);
+  const int M = ua_n_metrics(flags), F = ur_fields(M);
   if (raw_statistics == nullptr) return set_error(PDP_E_INVALID, "raw_statistics is NULL");
   if (M != 0 && metrics == nullptr) return set_error(PDP_E_INVALID, "metrics is NULL");
   if (M != 0 && std_noise == nullptr) return set_error(PDP_E_INVALID, "std_noise is NULL");
@@ -413,12 +341,8 @@ int pdp_utility_report(const int64_t* raw_statistics, const double* keep_probabi
               (const long long*)raw_statistics, M != 0 ? metrics : nullptr, is_public ? 1 : 0, key,
               (unsigned long long*)counts);
   if (rc != PDP_OK) return rc;
-  rc = launch("k_ur_hist", k_ur_hist, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, P, key, hist, n_tiles);
-  if (rc != PDP_OK) return rc;
-  rc = scan_u32(hist, kUrKeys * n_tiles, (unsigned*)(ws + w.chunks), st);
-  if (rc != PDP_OK) return rc;
-  rc = launch("k_ur_scatter", k_ur_scatter, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, P, key, order, hist,
-              n_tiles);
+  rc = tile_sort_pass<6, kUrSortTile>("k_ur_hist", "k_ur_scatter", P, kUrKeys, 0, key, UrEmit{order}, hist,
+                                      (unsigned*)(ws + w.chunks), st);
   if (rc != PDP_OK) return rc;
   const UrIn in{is_public ? nullptr : keep_probability, metrics, dsn};
   const unsigned gx = (unsigned)((ur_max_tiles(P) + kBlock / 64 - 1) / (kBlock / 64));

@@ -167,18 +167,9 @@ int pdp_filter_rows(const int64_t* privacy_id, const int64_t* partition, const u
   const int64_t n_tiles = (n_rows + kFilterTile - 1) / kFilterTile;
   const unsigned grid = (unsigned)(n_tiles < kFilterMaxGrid ? n_tiles : kFilterMaxGrid);
   const bool vec = (((uintptr_t)privacy_id | (uintptr_t)partition) & 15) == 0;
-  PDP_PROF_BEGIN("k_filter_rows", st);
-  if (vec)
-    hipLaunchKernelGGL(k_filter_rows<true>, dim3(grid), dim3(kFilterThreads), 0, st, privacy_id, partition, allowed,
-                       n_rows, n_partitions, out_privacy_id, out_partition, (unsigned long long*)out_count,
-                       (unsigned*)workspace);
-  else
-    hipLaunchKernelGGL(k_filter_rows<false>, dim3(grid), dim3(kFilterThreads), 0, st, privacy_id, partition, allowed,
-                       n_rows, n_partitions, out_privacy_id, out_partition, (unsigned long long*)out_count,
-                       (unsigned*)workspace);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch("k_filter_rows", vec ? k_filter_rows<true> : k_filter_rows<false>, dim3(grid), dim3(kFilterThreads), 0,
+                st, privacy_id, partition, allowed, n_rows, n_partitions, out_privacy_id, out_partition,
+                (unsigned long long*)out_count, (unsigned*)workspace);
 }
 
 int pdp_l0_impact_dropped(const int64_t* l0_count, int64_t upper_bound, const int64_t* candidates,
@@ -193,12 +184,8 @@ int pdp_l0_impact_dropped(const int64_t* l0_count, int64_t upper_bound, const in
   const int per_block = kScoreThreads / 64;
   const int64_t grid = (n_candidates + per_block - 1) / per_block;
   if (grid > 0x7FFFFFFF) return set_error(PDP_E_UNSUPPORTED, "pdp_l0_impact_dropped: too many candidates");
-  PDP_PROF_BEGIN("k_l0_impact_dropped", st);
-  hipLaunchKernelGGL(k_l0_impact_dropped, dim3((unsigned)grid), dim3(kScoreThreads), 0, st, l0_count,
-                     (long long)upper_bound, candidates, n_candidates, dropped);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch("k_l0_impact_dropped", k_l0_impact_dropped, dim3((unsigned)grid), dim3(kScoreThreads), 0, st, l0_count,
+                (long long)upper_bound, candidates, n_candidates, dropped);
 }
 
 }  // extern "C"

@@ -1753,14 +1753,6 @@ __global__ void __launch_bounds__(kFloatBlock) k_hp_float(PT t, const double* __
   }
 }
 
-#define PDP_HLAUNCH(name, st, ...)          \
-  do {                                      \
-    PDP_PROF_BEGIN(name, st);               \
-    hipLaunchKernelGGL(__VA_ARGS__);        \
-    PDP_PROF_END(st);                       \
-    PDP_HIP_CHECK(hipGetLastError());       \
-  } while (0)
-
 }  // namespace
 }  // namespace pdp
 
@@ -1848,11 +1840,12 @@ int hist_pairs_bucketed(const HCall& c, const int64_t* privacy_id, const int64_t
   unsigned long long* key2 = (unsigned long long*)(val1 + t.n);
   double* val2 = (double*)(key2 + t.n);
   const bool hv = value_kind != PDP_VALUE_NONE;
-  PDP_HLAUNCH("k_hb_count", st, k_hb_count, dim3((unsigned)t.n_tiles), dim3(kHbThreads), 0, st, t, privacy_id,
-              partition, cts, err);
-  PDP_HLAUNCH("k_hb_scan_tiles", st, k_hb_scan_tiles, dim3((unsigned)t.n_supers), dim3(kHbThreads), 0, st, t, cts,
-              sbase);
-  PDP_HLAUNCH("k_hb_scan_supers", st, k_hb_scan_supers, dim3(1), dim3(kHbFan), 0, st, t, sbase);
+  if (int rc = launch("k_hb_count", k_hb_count, dim3((unsigned)t.n_tiles), dim3(kHbThreads), 0, st, t, privacy_id,
+                      partition, cts, err); rc != PDP_OK) return rc;
+  if (int rc = launch("k_hb_scan_tiles", k_hb_scan_tiles, dim3((unsigned)t.n_supers), dim3(kHbThreads), 0, st, t, cts,
+                      sbase); rc != PDP_OK) return rc;
+  if (int rc = launch("k_hb_scan_supers", k_hb_scan_supers, dim3(1), dim3(kHbFan), 0, st, t,
+                      sbase); rc != PDP_OK) return rc;
   const size_t lds1 = hb_l1_lds(value_kind);
   const void* l1 = value_kind == PDP_VALUE_F64 ? (const void*)k_hb_l1<PDP_VALUE_F64>
                    : value_kind == PDP_VALUE_I64 ? (const void*)k_hb_l1<PDP_VALUE_I64>
@@ -1872,16 +1865,13 @@ int hist_pairs_bucketed(const HCall& c, const int64_t* privacy_id, const int64_t
   PDP_HIP_CHECK(hipMemsetAsync(bcnt, 0, (uint64_t)(t.nb + 1) * 4, st));
   PDP_HIP_CHECK(hipMemsetAsync(bcur, 0, (uint64_t)t.nb * 4, st));
   const unsigned g2 = (unsigned)(t.n_supers * kHbK);
-  PDP_HLAUNCH("k_hb_bcount", st, k_hb_bcount, dim3(g2), dim3(kHbL2Threads), 0, st, t, (const unsigned*)sbase,
-              (const unsigned long long*)key1, bcnt);
+  if (int rc = launch("k_hb_bcount", k_hb_bcount, dim3(g2), dim3(kHbL2Threads), 0, st, t, (const unsigned*)sbase,
+                      (const unsigned long long*)key1, bcnt); rc != PDP_OK) return rc;
   const int rc = scan_u32(bcnt, t.nb, (unsigned*)(ws + w.hb_bchunks), st);  // -> bucket starts
   if (rc != PDP_OK) return rc;
-  if (hv)
-    PDP_HLAUNCH("k_hb_l2", st, k_hb_l2<true>, dim3(g2), dim3(kHbL2Threads), 0, st, t, (const unsigned*)sbase,
-                (const unsigned long long*)key1, (const double*)val1, (const unsigned*)bcnt, bcur, key2, val2);
-  else
-    PDP_HLAUNCH("k_hb_l2", st, k_hb_l2<false>, dim3(g2), dim3(kHbL2Threads), 0, st, t, (const unsigned*)sbase,
-                (const unsigned long long*)key1, (const double*)val1, (const unsigned*)bcnt, bcur, key2, val2);
+  if (int rc = launch("k_hb_l2", hv ? k_hb_l2<true> : k_hb_l2<false>, dim3(g2), dim3(kHbL2Threads), 0, st, t,
+                      (const unsigned*)sbase, (const unsigned long long*)key1, (const double*)val1,
+                      (const unsigned*)bcnt, bcur, key2, val2); rc != PDP_OK) return rc;
   // mode: 1 = pair-sum list, 2 = privacy-id buckets' range-grouped records (+ R in word 3)
   PDP_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ctl, pid_buckets && t.hb_R ? 2u : 1u, 1, st));
   if (pid_buckets && t.hb_R) PDP_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(ctl + 3), (unsigned)t.hb_R, 1, st));
@@ -1918,24 +1908,15 @@ int hist_pairs_bucketed(const HCall& c, const int64_t* privacy_id, const int64_t
       const int64_t per = (t.nb + G - 1) / G;
       G = (t.nb + per - 1) / per;
       const PRec* pr = prec;
-      if (hv)
-        PDP_HLAUNCH("k_hb_prange", st, k_hb_prange<true>, dim3((unsigned)t.hb_R, (unsigned)G), dim3(kHbRangeThreads),
-                    0, st, t, (const unsigned*)bcnt, (const unsigned*)pruns, pr, pkstat, psum, c.H, minmax, per);
-      else
-        PDP_HLAUNCH("k_hb_prange", st, k_hb_prange<false>, dim3((unsigned)t.hb_R, (unsigned)G), dim3(kHbRangeThreads),
-                    0, st, t, (const unsigned*)bcnt, (const unsigned*)pruns, pr, pkstat, psum, c.H, minmax, per);
+      return launch("k_hb_prange", hv ? k_hb_prange<true> : k_hb_prange<false>, dim3((unsigned)t.hb_R, (unsigned)G),
+                    dim3(kHbRangeThreads), 0, st, t, (const unsigned*)bcnt, (const unsigned*)pruns, pr, pkstat, psum,
+                    c.H, minmax, per);
     }
     return PDP_OK;
   }
-  if (hv)
-    PDP_HLAUNCH("k_hb_pairs", st, k_hb_pairs<true>, dim3((unsigned)t.nb), dim3(kHbPairThreads), 0, st, t,
-                (const unsigned*)bcnt, (const unsigned long long*)key2, (const double*)val2, pidstat, pkstat, psum,
-                c.H, minmax, pairsum, ctl);
-  else
-    PDP_HLAUNCH("k_hb_pairs", st, k_hb_pairs<false>, dim3((unsigned)t.nb), dim3(kHbPairThreads), 0, st, t,
-                (const unsigned*)bcnt, (const unsigned long long*)key2, (const double*)val2, pidstat, pkstat, psum,
-                c.H, minmax, pairsum, ctl);
-  return PDP_OK;
+  return launch("k_hb_pairs", hv ? k_hb_pairs<true> : k_hb_pairs<false>, dim3((unsigned)t.nb), dim3(kHbPairThreads), 0,
+                st, t, (const unsigned*)bcnt, (const unsigned long long*)key2, (const double*)val2, pidstat, pkstat,
+                psum, c.H, minmax, pairsum, ctl);
 }
 
 // zero everything; k_h_rows + k_h_pairs (pair table, per-pid / per-partition
@@ -1955,7 +1936,8 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
   // and per-partition statistics for both
   if (!bucketed) PDP_HIP_CHECK(hipMemsetAsync(ws + w.slots, 0, w.pidstat - w.slots, st));
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.pidstat, 0, w.minmax - w.pidstat, st));  // pidstat .. psum
-  PDP_HLAUNCH("k_h_init", st, k_h_init, dim3(1), dim3(64), 0, st, (unsigned long long*)(ws + w.minmax));
+  if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, st,
+                      (unsigned long long*)(ws + w.minmax)); rc != PDP_OK) return rc;
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.fmax, 0, 2 * kSumBuckets * 8, st));
   PDP_HIP_CHECK(hipMemsetAsync(out->int_count, 0, 5 * kLogBins * 8, st));
   PDP_HIP_CHECK(hipMemsetAsync(out->int_sum, 0, 5 * kLogBins * 8, st));
@@ -1981,7 +1963,8 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
       PDP_HIP_CHECK(hipStreamSynchronize(st));
       if (!over) return PDP_OK;
       PDP_HIP_CHECK(hipMemsetAsync(ws + w.hb_ctl, 0, 16, st));
-      PDP_HLAUNCH("k_h_init", st, k_h_init, dim3(1), dim3(64), 0, st, (unsigned long long*)(ws + w.minmax));
+      if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, st,
+                          (unsigned long long*)(ws + w.minmax)); rc != PDP_OK) return rc;
       PDP_HIP_CHECK(hipMemsetAsync(out->int_count, 0, 5 * kLogBins * 8, st));
       PDP_HIP_CHECK(hipMemsetAsync(out->int_sum, 0, 5 * kLogBins * 8, st));
       PDP_HIP_CHECK(hipMemsetAsync(out->int_max, 0, 5 * kLogBins * 8, st));
@@ -1993,35 +1976,33 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
   unsigned* err = (unsigned*)(ws + w.err);
   unsigned* rbase = (unsigned*)(ws + w.rbase);
   const unsigned g = grid_for(t.n);
-  if (t.R <= kRegionLdsMax)
-    PDP_HLAUNCH("k_h_region_count", st, k_h_region_count<true>, dim3(grid_for(t.n, 1024)), dim3(kBlock), 0, st, t,
-                privacy_id, partition, rbase);
-  else
-    PDP_HLAUNCH("k_h_region_count", st, k_h_region_count<false>, dim3(g), dim3(kBlock), 0, st, t, privacy_id,
-                partition, rbase);
-  PDP_HLAUNCH("k_h_region_caps", st, k_h_region_caps, dim3(grid_for(t.R)), dim3(kBlock), 0, st, t.R, rbase);
+  const bool lds_regions = t.R <= kRegionLdsMax;
+  if (int rc = launch("k_h_region_count", lds_regions ? k_h_region_count<true> : k_h_region_count<false>,
+                      dim3(lds_regions ? grid_for(t.n, 1024) : g), dim3(kBlock), 0, st, t, privacy_id, partition,
+                      rbase); rc != PDP_OK) return rc;
+  if (int rc = launch("k_h_region_caps", k_h_region_caps, dim3(grid_for(t.R)), dim3(kBlock), 0, st, t.R,
+                      rbase); rc != PDP_OK) return rc;
   {
     const int rc = scan_u32(rbase, t.R, (unsigned*)(ws + w.rchunks), st);
     if (rc != PDP_OK) return rc;
   }
   switch (value_kind) {
     case PDP_VALUE_F64:
-      PDP_HLAUNCH("k_h_rows", st, k_h_rows<PDP_VALUE_F64>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
-                  value, rbase, slots, err);
+      if (int rc = launch("k_h_rows", k_h_rows<PDP_VALUE_F64>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
+                          value, rbase, slots, err); rc != PDP_OK) return rc;
       break;
     case PDP_VALUE_I64:
-      PDP_HLAUNCH("k_h_rows", st, k_h_rows<PDP_VALUE_I64>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
-                  value, rbase, slots, err);
+      if (int rc = launch("k_h_rows", k_h_rows<PDP_VALUE_I64>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
+                          value, rbase, slots, err); rc != PDP_OK) return rc;
       break;
     default:
-      PDP_HLAUNCH("k_h_rows", st, k_h_rows<PDP_VALUE_NONE>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
-                  value, rbase, slots, err);
+      if (int rc = launch("k_h_rows", k_h_rows<PDP_VALUE_NONE>, dim3(g), dim3(kBlock), 0, st, t, privacy_id,
+                          partition, value, rbase, slots, err); rc != PDP_OK) return rc;
   }
   const int64_t n_chunks = ((int64_t)t.cap + kPairsChunk - 1) / kPairsChunk;  // upper bound of the used slots
-  PDP_HLAUNCH("k_h_pairs", st, k_h_pairs, dim3((unsigned)n_chunks), dim3(kPairsBlock), 0, st, t, slots, rbase,
-              (unsigned long long*)(ws + w.pidstat), (unsigned long long*)(ws + w.pkstat), (double*)(ws + w.psum),
-              c.H, (unsigned long long*)(ws + w.minmax));
-  return PDP_OK;
+  return launch("k_h_pairs", k_h_pairs, dim3((unsigned)n_chunks), dim3(kPairsBlock), 0, st, t, slots, rbase,
+                (unsigned long long*)(ws + w.pidstat), (unsigned long long*)(ws + w.pkstat), (double*)(ws + w.psum),
+                c.H, (unsigned long long*)(ws + w.minmax));
 }
 
 // k_h_ids (partition part only when t.do_parts), lowers, float bins, final
@@ -2037,10 +2018,12 @@ int hist_finish(const HCall& c, const pdp_histogram_bins* out) {
   if (m > 0)
     // at most 256 workgroups: each flushes its small bins with one global
     // atomic per bin, and 2,048 of them made those flushes most of the kernel
-    PDP_HLAUNCH("k_h_ids", st, k_h_ids, dim3((unsigned)((m + kIdsThreads - 1) / kIdsThreads < 256 ? (m + kIdsThreads - 1) / kIdsThreads : 256)), dim3(kIdsThreads), 0, st, t,
-                (const unsigned long long*)(ws + w.pidstat), pkstat, psum, c.H, minmax);
-  PDP_HLAUNCH("k_h_lowers", st, k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, st, minmax,
-              out->float_lowers, out->float_n_lowers);
+    if (int rc = launch("k_h_ids", k_h_ids,
+                        dim3((unsigned)((m + kIdsThreads - 1) / kIdsThreads < 256 ? (m + kIdsThreads - 1) / kIdsThreads : 256)),
+                        dim3(kIdsThreads), 0, st, t, (const unsigned long long*)(ws + w.pidstat), pkstat, psum, c.H,
+                        minmax); rc != PDP_OK) return rc;
+  if (int rc = launch("k_h_lowers", k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, st,
+                      minmax, out->float_lowers, out->float_n_lowers); rc != PDP_OK) return rc;
   // one 1024-thread workgroup per CU (120 KB of LDS each)
   int dev = 0, cus = 256;
   PDP_HIP_CHECK(hipGetDevice(&dev));
@@ -2053,13 +2036,14 @@ int hist_finish(const HCall& c, const pdp_histogram_bins* out) {
   const unsigned* fctl = (const unsigned*)(ws + w.hb_ctl);
   const unsigned* fbstart = (const unsigned*)(w.hb_bcnt ? ws + w.hb_bcnt : nullptr);
   const PRec* fprec = (const PRec*)(ws + w.slots);
-  PDP_HLAUNCH("k_h_float", st, k_h_float<false>, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, fslots, fpairsum,
-              fctl, fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers, c.F);
-  PDP_HLAUNCH("k_h_float_max", st, k_h_float<true>, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, fslots,
-              fpairsum, fctl, fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers, c.F);
-  PDP_HLAUNCH("k_h_final", st, k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.H,
-              c.F, out->float_max, 0x1F);
-  return PDP_OK;
+  if (int rc = launch("k_h_float", k_h_float<false>, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, fslots,
+                      fpairsum, fctl, fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers,
+                      c.F); rc != PDP_OK) return rc;
+  if (int rc = launch("k_h_float_max", k_h_float<true>, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, fslots,
+                      fpairsum, fctl, fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers,
+                      c.F); rc != PDP_OK) return rc;
+  return launch("k_h_final", k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.H, c.F,
+                out->float_max, 0x1F);
 }
 
 }  // namespace
@@ -2157,7 +2141,8 @@ int pre_rows(const PCall& c, const int64_t* partition, const int64_t* count, con
   hipStream_t st = c.st;
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.err, 0, 16, st));
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.pkrows, 0, w.minmax - w.pkrows, st));  // pkrows .. psum
-  PDP_HLAUNCH("k_h_init", st, k_h_init, dim3(1), dim3(64), 0, st, (unsigned long long*)(ws + w.minmax));
+  if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, st,
+                      (unsigned long long*)(ws + w.minmax)); rc != PDP_OK) return rc;
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.fmax, 0, w.total - w.fmax, st));  // fmax, weight sums, weight table
   PDP_HIP_CHECK(hipMemsetAsync(out->int_count, 0, 5 * kLogBins * 8, st));
   PDP_HIP_CHECK(hipMemsetAsync(out->int_sum, 0, 5 * kLogBins * 8, st));
@@ -2169,12 +2154,11 @@ int pre_rows(const PCall& c, const int64_t* partition, const int64_t* count, con
   if (partition == nullptr || count == nullptr || sum == nullptr || n_partitions_of_pid == nullptr ||
       n_contributions_of_pid == nullptr)
     return set_error(PDP_E_INVALID, "NULL column");
-  PDP_HLAUNCH("k_hp_rows", st, k_hp_rows, dim3(grid_for(t.n, 2048)), dim3(kBlock), 0, st, t, partition, count, sum,
-              n_partitions_of_pid, n_contributions_of_pid, (unsigned long long*)(ws + w.pkrows),
-              (unsigned long long*)(ws + w.pkcount), (double*)(ws + w.psum), c.H,
-              (unsigned long long*)(ws + w.minmax), (double*)(ws + w.wsmall), (WSlot*)(ws + w.wtab),
-              (unsigned*)(ws + w.err));
-  return PDP_OK;
+  return launch("k_hp_rows", k_hp_rows, dim3(grid_for(t.n, 2048)), dim3(kBlock), 0, st, t, partition, count, sum,
+                n_partitions_of_pid, n_contributions_of_pid, (unsigned long long*)(ws + w.pkrows),
+                (unsigned long long*)(ws + w.pkcount), (double*)(ws + w.psum), c.H,
+                (unsigned long long*)(ws + w.minmax), (double*)(ws + w.wsmall), (WSlot*)(ws + w.wtab),
+                (unsigned*)(ws + w.err));
 }
 
 // weighted L0 / L1 bins, partition histograms (t.do_parts), lowers, float bins
@@ -2187,13 +2171,15 @@ int pre_finish(const PCall& c, const double* sum, const pdp_histogram_bins* out)
   const unsigned long long* pkrows = (const unsigned long long*)(ws + w.pkrows);
   const double* psum = (const double*)(ws + w.psum);
   const int64_t nw = 2 * kWSmall + (int64_t)t.cap;
-  PDP_HLAUNCH("k_hp_weights", st, k_hp_weights, dim3((unsigned)((nw + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-              (const double*)(ws + w.wsmall), (const WSlot*)(ws + w.wtab), t.cap, c.H);
-  if (t.do_parts && t.P > 0)
-    PDP_HLAUNCH("k_hp_ids", st, k_hp_ids, dim3(grid_for(t.P, 2048)), dim3(kBlock), 0, st, t, pkrows,
-                (const unsigned long long*)(ws + w.pkcount), psum, c.H, minmax);
-  PDP_HLAUNCH("k_h_lowers", st, k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, st, minmax,
-              out->float_lowers, out->float_n_lowers);
+  if (int rc = launch("k_hp_weights", k_hp_weights, dim3((unsigned)((nw + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                      (const double*)(ws + w.wsmall), (const WSlot*)(ws + w.wtab), t.cap,
+                      c.H); rc != PDP_OK) return rc;
+  if (t.do_parts && t.P > 0) {
+    if (int rc = launch("k_hp_ids", k_hp_ids, dim3(grid_for(t.P, 2048)), dim3(kBlock), 0, st, t, pkrows,
+                        (const unsigned long long*)(ws + w.pkcount), psum, c.H, minmax); rc != PDP_OK) return rc;
+  }
+  if (int rc = launch("k_h_lowers", k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, st,
+                      minmax, out->float_lowers, out->float_n_lowers); rc != PDP_OK) return rc;
   int dev = 0, cus = 256;
   PDP_HIP_CHECK(hipGetDevice(&dev));
   PDP_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -2201,11 +2187,10 @@ int pre_finish(const PCall& c, const double* sum, const pdp_histogram_bins* out)
   int64_t gf = (mf + kFloatBlock - 1) / kFloatBlock;
   gf = gf < 1 ? 1 : (gf < cus ? gf : cus);
   if (t.n > 0 && sum == nullptr) return set_error(PDP_E_INVALID, "NULL column");
-  PDP_HLAUNCH("k_hp_float", st, k_hp_float, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, sum,
-              pkrows, psum, out->float_lowers, out->float_n_lowers, c.F);
-  PDP_HLAUNCH("k_h_final", st, k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.H,
-              c.F, out->float_max, (1 << H_LINF) | (1 << H_COUNT) | (1 << H_PIDS));
-  return PDP_OK;
+  if (int rc = launch("k_hp_float", k_hp_float, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, sum, pkrows, psum,
+                      out->float_lowers, out->float_n_lowers, c.F); rc != PDP_OK) return rc;
+  return launch("k_h_final", k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.H, c.F,
+                out->float_max, (1 << H_LINF) | (1 << H_COUNT) | (1 << H_PIDS));
 }
 
 }  // namespace
@@ -2266,9 +2251,8 @@ int pdp_dataset_histograms_weight_bins(const uint64_t* keys, const double* weigh
   hipStream_t st = (hipStream_t)stream;
   const pdp::IntHists H{(unsigned long long*)out->int_count, (unsigned long long*)out->int_sum,
                         (unsigned long long*)out->int_max};
-  PDP_HLAUNCH("k_hp_weight_list", st, pdp::k_hp_weight_list, dim3(pdp::grid_for(n, (int64_t)1 << 30)),
-              dim3(pdp::kBlock), 0, st, (const unsigned long long*)keys, weights, n, H);
-  return PDP_OK;
+  return pdp::launch("k_hp_weight_list", pdp::k_hp_weight_list, dim3(pdp::grid_for(n, (int64_t)1 << 30)),
+                dim3(pdp::kBlock), 0, st, (const unsigned long long*)keys, weights, n, H);
 }
 
 int pdp_dataset_histograms_preaggregated_finish(const double* sum, int64_t n_rows, int64_t n_partitions,

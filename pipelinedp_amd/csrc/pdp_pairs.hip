@@ -47,7 +47,7 @@
 // keeps its maximum (pool[offset + cap - 1]), so membership is the same test
 // `key <= pool[offset + cap - 1]` in both modes; Linf's kept rows of heavy
 // pairs are then summed by a second pass over the rows (k_pair_rows_kept).
-#include "pdp_internal.h"
+#include "pdp_segments.h"
 
 namespace pdp {
 namespace {
@@ -541,14 +541,6 @@ int dispatch_vk(int value_kind, A&&... args) {
   }
 }
 
-#define PDP_LAUNCH(name, st, ...)                                           \
-  do {                                                                      \
-    PDP_PROF_BEGIN(name, st);                                               \
-    hipLaunchKernelGGL(__VA_ARGS__);                                        \
-    PDP_PROF_END(st);                                                       \
-    PDP_HIP_CHECK(hipGetLastError());                                       \
-  } while (0)
-
 struct BoundArgs {
   const PT* t;
   const int64_t* pid;
@@ -580,26 +572,25 @@ struct RunBound {
     auto run_select = [&](unsigned* n_list, const unsigned* off, const unsigned* cnt, int cap,
                           unsigned long long* pool) -> int {
       const int64_t ub = t.n / ((int64_t)cap + 1) + 1;
-      PDP_LAUNCH("k_radix_select", st, k_radix_select, dim3((unsigned)ub), dim3(kSelBlock), 0, st, hlist, n_list, off, cnt,
-                 (unsigned)cap, pool);
-      return PDP_OK;
+      return launch("k_radix_select", k_radix_select, dim3((unsigned)ub), dim3(kSelBlock), 0, st, hlist, n_list, off,
+                    cnt, (unsigned)cap, pool);
     };
     if (t.maxc > 0) {
-      PDP_LAUNCH("k_pid_count", st, k_pid_count, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.allowed, pid_cnt,
-                 err);
+      if (int rc = launch("k_pid_count", k_pid_count, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.allowed,
+                          pid_cnt, err); rc != PDP_OK) return rc;
       const unsigned gu = grid_for(t.U);
-      PDP_LAUNCH("k_sketch_len", st, k_sketch_len, dim3(gu), dim3(kBlock), 0, st, pid_cnt, nullptr, nullptr, t.U,
-                 (unsigned)t.maxc, t.sel_maxc, pid_off, hlist, hcount);
+      if (int rc = launch("k_sketch_len", k_sketch_len, dim3(gu), dim3(kBlock), 0, st, pid_cnt, nullptr, nullptr, t.U,
+                          (unsigned)t.maxc, t.sel_maxc, pid_off, hlist, hcount); rc != PDP_OK) return rc;
       int rc = scan_u32(pid_off, t.U, (unsigned*)(ws + w.pid_chunks), st);
       if (rc != PDP_OK) return rc;
       if (t.sel_maxc) {
-        PDP_LAUNCH("k_pid_fill", st, k_pid_fill, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.allowed, pid_cnt,
-                   pid_off, pid_fill, pid_pool);
+        if (int rc = launch("k_pid_fill", k_pid_fill, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.allowed,
+                            pid_cnt, pid_off, pid_fill, pid_pool); rc != PDP_OK) return rc;
         rc = run_select(hcount, pid_off, pid_cnt, t.maxc, pid_pool);
         if (rc != PDP_OK) return rc;
       } else {
-        PDP_LAUNCH("k_pid_sketch", st, k_pid_sketch, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.allowed,
-                   pid_cnt, pid_off, pid_pool);
+        if (int rc = launch("k_pid_sketch", k_pid_sketch, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.allowed,
+                            pid_cnt, pid_off, pid_pool); rc != PDP_OK) return rc;
       }
     }
     double* f0 = w.f0 ? (double*)(ws + w.f0) : nullptr;
@@ -610,44 +601,49 @@ struct RunBound {
     const int64_t C = (int64_t)t.mask + 1;
     const unsigned gc = grid_for(C);
     if (t.linf == 0) {
-      PDP_LAUNCH("k_pair_insert", st, (k_pair_insert<VK, true>), dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk,
-                 a.value, a.allowed, pid_cnt, pid_off, pid_pool, keys, cnt, f0, f1, f2, err);
+      if (int rc = launch("k_pair_insert", k_pair_insert<VK, true>, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk,
+                          a.value, a.allowed, pid_cnt, pid_off, pid_pool, keys, cnt, f0, f1, f2,
+                          err); rc != PDP_OK) return rc;
     } else {
-      PDP_LAUNCH("k_pair_insert", st, (k_pair_insert<VK, false>), dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk,
-                 a.value, a.allowed, pid_cnt, pid_off, pid_pool, keys, cnt, f0, f1, f2, err);
+      if (int rc = launch("k_pair_insert", k_pair_insert<VK, false>, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk,
+                          a.value, a.allowed, pid_cnt, pid_off, pid_pool, keys, cnt, f0, f1, f2,
+                          err); rc != PDP_OK) return rc;
     }
     uint8_t* keep = nullptr;
     if (t.l0 > 0) {  // cross-partition sampling over the table's distinct pairs
       keep = (uint8_t*)(ws + w.pkeep);
-      PDP_LAUNCH("k_pid_pairs", st, k_pid_pairs, dim3(gc), dim3(kBlock), 0, st, t, keys, pid_cnt);
+      if (int rc = launch("k_pid_pairs", k_pid_pairs, dim3(gc), dim3(kBlock), 0, st, t, keys,
+                          pid_cnt); rc != PDP_OK) return rc;
       const unsigned gu = grid_for(t.U);
-      PDP_LAUNCH("k_sketch_len", st, k_sketch_len, dim3(gu), dim3(kBlock), 0, st, pid_cnt, nullptr, nullptr, t.U,
-                 (unsigned)t.l0, t.sel_l0, pid_off, hlist, hcount + 1);
+      if (int rc = launch("k_sketch_len", k_sketch_len, dim3(gu), dim3(kBlock), 0, st, pid_cnt, nullptr, nullptr, t.U,
+                          (unsigned)t.l0, t.sel_l0, pid_off, hlist, hcount + 1); rc != PDP_OK) return rc;
       int rc = scan_u32(pid_off, t.U, (unsigned*)(ws + w.pid_chunks), st);
       if (rc != PDP_OK) return rc;
-      PDP_LAUNCH("k_pid_l0", st, k_pid_l0, dim3(gc), dim3(kBlock), 0, st, t, keys, pid_cnt, pid_off, pid_fill,
-                 pid_pool);
+      if (int rc = launch("k_pid_l0", k_pid_l0, dim3(gc), dim3(kBlock), 0, st, t, keys, pid_cnt, pid_off, pid_fill,
+                          pid_pool); rc != PDP_OK) return rc;
       if (t.sel_l0) {
         rc = run_select(hcount + 1, pid_off, pid_cnt, t.l0, pid_pool);
         if (rc != PDP_OK) return rc;
       }
-      PDP_LAUNCH("k_pair_keep", st, k_pair_keep, dim3(gc), dim3(kBlock), 0, st, t, keys, pid_cnt, pid_off, pid_pool,
-                 keep);
+      if (int rc = launch("k_pair_keep", k_pair_keep, dim3(gc), dim3(kBlock), 0, st, t, keys, pid_cnt, pid_off,
+                          pid_pool, keep); rc != PDP_OK) return rc;
     }
     if (t.linf == 0) return PDP_OK;
     unsigned* pair_off = (unsigned*)(ws + w.pair_off);
     unsigned long long* pair_pool = (unsigned long long*)(ws + w.pair_pool);
-    PDP_LAUNCH("k_sketch_len", st, k_sketch_len, dim3(gc), dim3(kBlock), 0, st, cnt, keys, keep, C,
-               (unsigned)t.linf, t.sel_linf, pair_off, hlist, hcount + 2);
+    if (int rc = launch("k_sketch_len", k_sketch_len, dim3(gc), dim3(kBlock), 0, st, cnt, keys, keep, C,
+                        (unsigned)t.linf, t.sel_linf, pair_off, hlist, hcount + 2); rc != PDP_OK) return rc;
     int rc = scan_u32(pair_off, C, (unsigned*)(ws + w.pair_chunks), st);
     if (rc != PDP_OK) return rc;
-    PDP_LAUNCH("k_pair_rows", st, k_pair_rows<VK>, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.value,
-               a.allowed, keys, cnt, pair_off, keep, (unsigned*)(ws + w.pair_fill), pair_pool, f0, f1, f2);
+    if (int rc = launch("k_pair_rows", k_pair_rows<VK>, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk, a.value,
+                        a.allowed, keys, cnt, pair_off, keep, (unsigned*)(ws + w.pair_fill), pair_pool, f0, f1,
+                        f2); rc != PDP_OK) return rc;
     if (t.sel_linf) {
       rc = run_select(hcount + 2, pair_off, cnt, t.linf, pair_pool);
       if (rc != PDP_OK) return rc;
-      PDP_LAUNCH("k_pair_rows_kept", st, k_pair_rows_kept<VK>, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk,
-                 a.value, a.allowed, keys, cnt, pair_off, keep, pair_pool, f0, f1, f2);
+      if (int rc = launch("k_pair_rows_kept", k_pair_rows_kept<VK>, dim3(g), dim3(kBlock), 0, st, t, a.pid, a.pk,
+                          a.value, a.allowed, keys, cnt, pair_off, keep, pair_pool, f0, f1,
+                          f2); rc != PDP_OK) return rc;
     }
     return PDP_OK;
   }
@@ -677,13 +673,13 @@ struct RunReduce {
     const unsigned long long* pool = t.linf > 0 ? (const unsigned long long*)(ws + w.pair_pool) : nullptr;
     const uint8_t* keep = t.l0 > 0 ? (const uint8_t*)(ws + w.pkeep) : nullptr;
     if (t.linf == 0) {
-      PDP_LAUNCH("k_pair_reduce", a.st, (k_pair_reduce<VK, true>), dim3(gc), dim3(kBlock), 0, a.st, t, a.value,
-                 (const unsigned long long*)(ws + w.keys), (const unsigned*)(ws + w.cnt), pair_off, pool, f0, f1, f2,
-                 keep, a.acc);
+      if (int rc = launch("k_pair_reduce", k_pair_reduce<VK, true>, dim3(gc), dim3(kBlock), 0, a.st, t, a.value,
+                          (const unsigned long long*)(ws + w.keys), (const unsigned*)(ws + w.cnt), pair_off, pool, f0,
+                          f1, f2, keep, a.acc); rc != PDP_OK) return rc;
     } else {
-      PDP_LAUNCH("k_pair_reduce", a.st, (k_pair_reduce<VK, false>), dim3(gc), dim3(kBlock), 0, a.st, t,
-                 a.value, (const unsigned long long*)(ws + w.keys), (const unsigned*)(ws + w.cnt), pair_off, pool, f0,
-                 f1, f2, keep, a.acc);
+      if (int rc = launch("k_pair_reduce", k_pair_reduce<VK, false>, dim3(gc), dim3(kBlock), 0, a.st, t, a.value,
+                          (const unsigned long long*)(ws + w.keys), (const unsigned*)(ws + w.cnt), pair_off, pool, f0,
+                          f1, f2, keep, a.acc); rc != PDP_OK) return rc;
     }
     return PDP_OK;
   }
@@ -694,9 +690,7 @@ struct RunUnits {
   static int run(const PT& t, const int64_t* pk, const void* value, const uint8_t* allowed,
                  pdp_partition_accumulators part, unsigned* err, hipStream_t st) {
     const unsigned g = grid_for(t.n);
-    PDP_LAUNCH("k_rows_units", st, k_rows_units<VK>, dim3(g), dim3(kBlock), 0, st, t, pk, value, allowed, part,
-               err);
-    return PDP_OK;
+    return launch("k_rows_units", k_rows_units<VK>, dim3(g), dim3(kBlock), 0, st, t, pk, value, allowed, part, err);
   }
 };
 
@@ -707,14 +701,12 @@ struct RunUnits {
 //   k_vs_mark     one pass over the key columns: mark[i] = partition of a kept
 //                 row (else ~0), and rows per partition
 //   scan_u32      -> segment offsets; k_vs_scatter: kept row indices by partition
-//   k_vs_reduce   one wave per work item, lanes across coordinates (8 or 16 B
-//                 per lane), 64 / lanes-per-row rows in flight.  Items: every
-//                 partition with <= kVsTile kept rows (summed whole, added to
-//                 the caller's accumulator by its only writer), and every tile
-//                 of kVsTile consecutive entries of the kept-row list, which
-//                 sums the pieces of the (at most two) longer partitions it
-//                 overlaps into partial[tile][0 | 1]
-//   k_vs_combine  one wave per longer partition adds its tiles' partials
+//   k_vs_reduce / k_vs_combine
+//                 the segment reduce of pdp_segments.h over the kept-row list
+//                 with tiles of kVsTile entries, lanes across coordinates (8 or
+//                 16 B per lane), 64 / lanes-per-row rows in flight; a whole
+//                 partition's sum is added to the caller's accumulator by its
+//                 only writer
 // No atomic touches a double: a hot partition is split over the tiles' waves.
 constexpr unsigned kVsTile = 1024;
 constexpr unsigned kVsNone = ~0u;
@@ -723,7 +715,7 @@ struct VWs {
   uint64_t mark, rows, pcnt, pcur, chunks, partial, total;
 };
 
-__host__ __device__ inline int64_t vs_tiles(int64_t n) { return (n + kVsTile - 1) / kVsTile; }
+inline int64_t vs_tiles(int64_t n) { return seg_tiles<kVsTile>(n); }
 
 VWs vlayout(const pdp_bound_config* c, int d) {
   VWs v{};
@@ -871,17 +863,6 @@ __device__ __forceinline__ VsVal<V> vs_sum(const double* __restrict__ src, const
   return s;
 }
 
-// partition holding entry r of the kept-row list: the p with off[p] <= r < off[p + 1]
-// (r < off[P]; off is non-decreasing with off[0] = 0)
-__device__ __forceinline__ int64_t vs_partition_of(const unsigned* __restrict__ off, int64_t P, uint64_t r) {
-  int64_t lo = 0, hi = P;  // smallest q in [1, P] with off[q] > r
-  while (lo + 1 < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((uint64_t)off[mid] > r) hi = mid; else lo = mid;
-  }
-  return hi - 1;
-}
-
 struct VsGeom {
   int d;        // vector_size
   int cols;     // d / V lane columns
@@ -894,56 +875,28 @@ __global__ void __launch_bounds__(kBlock) k_vs_reduce(VsGeom g, int64_t n, int64
                                                       const unsigned* __restrict__ rows,
                                                       const unsigned* __restrict__ off, double* acc,
                                                       double* partial) {
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63);
   const int slot = lane >> g.log2_g;
   const int64_t col = (int64_t)(lane & ((1 << g.log2_g) - 1)) + (int64_t)blockIdx.y * 64;
   const bool active = col < g.cols;
-  const uint64_t total = off[P];
-  const int64_t tiles = vs_tiles(n), items = P + tiles;
-  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t it = (int64_t)blockIdx.x * (kBlock / 64) + wave; it < items; it += wstride) {
-    if (it < P) {  // a partition of at most kVsTile kept rows, whole
-      const uint64_t a = off[it], b = off[it + 1];
-      if (b <= a || b - a > kVsTile || b > total) continue;
-      const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, a, b, slot, g.log2_g, col, active);
-      if (slot == 0 && active) vs_store<V>(acc + (uint64_t)it * g.d + col * V, s, true);
-      continue;
-    }
-    const uint64_t tile = (uint64_t)(it - P);
-    const uint64_t r0 = tile * kVsTile;
-    if (r0 >= total) continue;
-    const uint64_t r1 = r0 + kVsTile < total ? r0 + kVsTile : total;
-    const int64_t pf = vs_partition_of(off, P, r0), pl = vs_partition_of(off, P, r1 - 1);
-    if (off[pf + 1] - off[pf] > kVsTile) {
-      const uint64_t e = off[pf + 1] < r1 ? off[pf + 1] : r1;
-      const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, r0, e, slot, g.log2_g, col, active);
-      if (slot == 0 && active) vs_store<V>(partial + (tile * 2) * g.d + col * V, s, false);
-    }
-    if (pl != pf && off[pl + 1] - off[pl] > kVsTile) {
-      const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, off[pl], r1, slot, g.log2_g, col, active);
-      if (slot == 0 && active) vs_store<V>(partial + (tile * 2 + 1) * g.d + col * V, s, false);
-    }
-  }
+  // an empty partition is skipped: a whole partition is added to the caller's accumulator
+  seg_for_each_piece<kVsTile, false>(off, P, n, off[P], [&](uint64_t a, uint64_t b, SegDst dst) {
+    const VsVal<V> s = vs_sum<V>(vectors, rows, (uint64_t)g.d, a, b, slot, g.log2_g, col, active);
+    if (slot == 0 && active) vs_store<V>((dst.whole ? acc : partial) + dst.at * g.d + col * V, s, dst.whole);
+  });
 }
 
-// partitions of more than kVsTile kept rows: tile t holds the partition's piece
-// in partial[t][0] if the partition owns the tile's first entry, else in [t][1]
-// (only its first tile can)
+// partitions of more than kVsTile kept rows: the partials are rows of 2 d doubles
 template <int V>
 __global__ void __launch_bounds__(kBlock) k_vs_combine(VsGeom g, int64_t P, const unsigned* __restrict__ off,
                                                        const double* __restrict__ partial, double* acc) {
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63);
   const int slot = lane >> g.log2_g;
   const int64_t col = (int64_t)(lane & ((1 << g.log2_g) - 1)) + (int64_t)blockIdx.y * 64;
   const bool active = col < g.cols;
-  const uint64_t total = off[P];
-  const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t p = (int64_t)blockIdx.x * (kBlock / 64) + wave; p < P; p += wstride) {
-    const uint64_t a = off[p], b = off[p + 1];
-    if (b <= a || b - a <= kVsTile || b > total) continue;
-    const uint64_t t0 = a / kVsTile, t1 = (b - 1) / kVsTile;
+  seg_for_each_long<kVsTile>(off, P, off[P], [&](int64_t p, uint64_t t0, uint64_t t1, bool first_in_slot_1) {
     VsVal<V> s;
-    if (a == t0 * kVsTile) {  // every piece in slot [t][0]: rows of 2 d doubles
+    if (!first_in_slot_1) {  // every piece in slot [t][0]
       s = vs_sum<V>(partial, nullptr, 2 * (uint64_t)g.d, t0, t1 + 1, slot, g.log2_g, col, active);
     } else {
       s = vs_sum<V>(partial, nullptr, 2 * (uint64_t)g.d, t0 + 1, t1 + 1, slot, g.log2_g, col, active);
@@ -953,7 +906,7 @@ __global__ void __launch_bounds__(kBlock) k_vs_combine(VsGeom g, int64_t P, cons
       }
     }
     if (slot == 0 && active) vs_store<V>(acc + (uint64_t)p * g.d + col * V, s, true);
-  }
+  });
 }
 
 template <int V>
@@ -962,11 +915,10 @@ int launch_vs(const VsGeom& g, int64_t n, int64_t P, const double* vectors, cons
   const unsigned gy = g.log2_g == 6 ? (unsigned)((g.cols + 63) / 64) : 1u;
   const int64_t items = P + vs_tiles(n);
   const unsigned gx = grid_for(items * 64, 8192);
-  PDP_LAUNCH("k_vs_reduce", st, k_vs_reduce<V>, dim3(gx, gy), dim3(kBlock), 0, st, g, n, P, vectors, rows, off, acc,
-             partial);
+  if (int rc = launch("k_vs_reduce", k_vs_reduce<V>, dim3(gx, gy), dim3(kBlock), 0, st, g, n, P, vectors, rows, off,
+                      acc, partial); rc != PDP_OK) return rc;
   const unsigned gp = grid_for(P * 64, 8192);
-  PDP_LAUNCH("k_vs_combine", st, k_vs_combine<V>, dim3(gp, gy), dim3(kBlock), 0, st, g, P, off, partial, acc);
-  return PDP_OK;
+  return launch("k_vs_combine", k_vs_combine<V>, dim3(gp, gy), dim3(kBlock), 0, st, g, P, off, partial, acc);
 }
 
 }  // namespace
@@ -1001,11 +953,12 @@ int pairs_vector_sum(const pdp_bound_config* c, const int64_t* pid, const int64_
     tb.keep = t.l0 > 0 ? (const uint8_t*)(ws + w.pkeep) : nullptr;
   }
   const unsigned g = grid_for(n);
-  PDP_LAUNCH("k_vs_mark", st, k_vs_mark, dim3(g), dim3(kBlock), 0, st, t, tb, c->rows_are_units ? nullptr : pid, pk,
-             allowed, mark, pcnt, (unsigned*)(ws + w.err));
+  if (int rc = launch("k_vs_mark", k_vs_mark, dim3(g), dim3(kBlock), 0, st, t, tb, c->rows_are_units ? nullptr : pid,
+                      pk, allowed, mark, pcnt, (unsigned*)(ws + w.err)); rc != PDP_OK) return rc;
   const int rc = scan_u32(pcnt, P, (unsigned*)(ws + v.chunks), st);
   if (rc != PDP_OK) return rc;
-  PDP_LAUNCH("k_vs_scatter", st, k_vs_scatter, dim3(g), dim3(kBlock), 0, st, n, P, mark, pcnt, pcur, rows);
+  if (int rc = launch("k_vs_scatter", k_vs_scatter, dim3(g), dim3(kBlock), 0, st, n, P, mark, pcnt, pcur,
+                      rows); rc != PDP_OK) return rc;
   double* partial = (double*)(ws + v.partial);
   // 16 B per lane where every row and the accumulator rows are 16-byte aligned
   const bool wide = d % 2 == 0 && ((((uintptr_t)vectors) | ((uintptr_t)vector_acc)) & 15) == 0;
@@ -1071,9 +1024,8 @@ int pairs_reduce(const pdp_bound_config* c, const void* value, char* ws, const p
   const PT t = make_pt(c);
   if (c->rows_are_units) {
     const unsigned g = grid_for(c->n_partitions);
-    PDP_LAUNCH("k_add_partials", st, k_add_partials, dim3(g), dim3(kBlock), 0, st, c->n_partitions, c->flags,
-               partials(ws, w), acc);
-    return PDP_OK;
+    return launch("k_add_partials", k_add_partials, dim3(g), dim3(kBlock), 0, st, c->n_partitions, c->flags,
+                  partials(ws, w), acc);
   }
   if (c->n_rows == 0) return PDP_OK;
   const ReduceArgs a{&t, value, ws, &w, acc, st};

@@ -110,10 +110,8 @@ int pdp_owner_mismatches(const int64_t* ids, int64_t n, int32_t world, int32_t r
   if (n == 0) return PDP_OK;
   const int64_t want = (n + 2 * pdp::kBlock - 1) / (2 * pdp::kBlock);
   const unsigned grid = (unsigned)(want < 4096 ? want : 4096);
-  hipLaunchKernelGGL(pdp::k_owner_mismatches, dim3(grid), dim3(pdp::kBlock), 0, st, ids, n, (int)world, (int)rank,
-                     mismatches);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return pdp::launch(nullptr, pdp::k_owner_mismatches, dim3(grid), dim3(pdp::kBlock), 0, st, ids, n, (int)world,
+                     (int)rank, mismatches);
 }
 
 

@@ -450,16 +450,10 @@ int pdp_select_partitions(const pdp_select_config* cfg, const int64_t* row_count
   const bool gauss = (cfg->strategy == PDP_SELECT_LAPLACE_THRESHOLDING ||
                       cfg->strategy == PDP_SELECT_GAUSSIAN_THRESHOLDING) &&
                      cfg->noise.kind == PDP_NOISE_GAUSSIAN && cfg->noise.granularity != 0.0;
-  PDP_PROF_BEGIN("k_select", (hipStream_t)stream);
-  if (gauss)  // ~20 partitions per lane (a full chip: 2,048 workgroups of 4 waves)
-    hipLaunchKernelGGL(k_select_gauss, dim3(grid_for(cfg->n_partitions, 2048)), dim3(kBlock), 0, (hipStream_t)stream,
-                       *cfg, row_count, keep, noised_count);
-  else
-    hipLaunchKernelGGL(k_select, dim3(grid_for(cfg->n_partitions)), dim3(kBlock), 0, (hipStream_t)stream,
-                       *cfg, row_count, keep, noised_count);
-  PDP_PROF_END((hipStream_t)stream);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  // Gaussian thresholding: ~20 partitions per lane (a full chip: 2,048 workgroups of 4 waves)
+  return launch("k_select", gauss ? k_select_gauss : k_select,
+                dim3(gauss ? grid_for(cfg->n_partitions, 2048) : grid_for(cfg->n_partitions)), dim3(kBlock), 0,
+                (hipStream_t)stream, *cfg, row_count, keep, noised_count);
 }
 
 int pdp_compact_workspace_bytes(int64_t n, uint64_t* bytes) {
@@ -483,19 +477,11 @@ int pdp_compact(const uint8_t* keep, int64_t n, int64_t* out_index, int64_t* out
   if (keep == nullptr || out_index == nullptr) return pdp::set_error(PDP_E_INVALID, "NULL argument");
   const int64_t nb = (n + kCompactChunk - 1) / kCompactChunk;
   int64_t* bc = (int64_t*)workspace;
-  PDP_PROF_BEGIN("k_compact_count", st);
-  hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nb), dim3(kBlock), 0, st, keep, n, bc);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_compact_scan", st);
-  hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(kBlock), 0, st, bc, nb, out_count);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  PDP_PROF_BEGIN("k_compact_write", st);
-  hipLaunchKernelGGL(k_compact_write, dim3((unsigned)nb), dim3(kBlock), 0, st, keep, n, bc, out_index);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  int rc = launch("k_compact_count", k_compact_count, dim3((unsigned)nb), dim3(kBlock), 0, st, keep, n, bc);
+  if (rc != PDP_OK) return rc;
+  rc = launch("k_compact_scan", k_compact_scan, dim3(1), dim3(kBlock), 0, st, bc, nb, out_count);
+  if (rc != PDP_OK) return rc;
+  return launch("k_compact_write", k_compact_write, dim3((unsigned)nb), dim3(kBlock), 0, st, keep, n, bc, out_index);
 }
 
 int pdp_noise_metrics(const pdp_metric_op* ops, int32_t n_ops, const int64_t* index, int64_t n_kept,
@@ -550,13 +536,9 @@ int pdp_noise_metrics(const pdp_metric_op* ops, int32_t n_ops, const int64_t* in
   // usually P): a grid-stride loop over at most 2,048 blocks, not one block per
   // 256 draws of every partition (C3: 7,813 mostly idle blocks, 34 us)
   const unsigned grid = grid_for(n_kept << log2_g) < 2048u ? grid_for(n_kept << log2_g) : 2048u;
-  PDP_PROF_BEGIN("k_noise_metrics", (hipStream_t)stream);
-  hipLaunchKernelGGL(k_noise_metrics, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pack,
-                     n_ops, log2_g, index, n_kept, n_kept_dev, partition_offset, *acc, sum_is_int, noised_count,
-                     out, out_stride, seed);
-  PDP_PROF_END((hipStream_t)stream);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch("k_noise_metrics", k_noise_metrics, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pack, n_ops,
+                log2_g, index, n_kept, n_kept_dev, partition_offset, *acc, sum_is_int, noised_count, out, out_stride,
+                seed);
 }
 
 int pdp_add_noise(const void* values, int32_t value_kind, int64_t n, const pdp_noise_params* noise,
@@ -572,16 +554,8 @@ int pdp_add_noise(const void* values, int32_t value_kind, int64_t n, const pdp_n
     return pdp::set_error(PDP_E_INVALID, "values and out must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int64_t pairs = (n + 1) >> 1;
-  PDP_PROF_BEGIN("k_add_noise", st);
-  if (value_kind == PDP_VALUE_I64)
-    hipLaunchKernelGGL(k_add_noise<PDP_VALUE_I64>, dim3(grid_for(pairs)), dim3(kBlock), 0, st, values, n,
-                       *noise, seed, index_offset, out);
-  else
-    hipLaunchKernelGGL(k_add_noise<PDP_VALUE_F64>, dim3(grid_for(pairs)), dim3(kBlock), 0, st, values, n,
-                       *noise, seed, index_offset, out);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch("k_add_noise", value_kind == PDP_VALUE_I64 ? k_add_noise<PDP_VALUE_I64> : k_add_noise<PDP_VALUE_F64>,
+                dim3(grid_for(pairs)), dim3(kBlock), 0, st, values, n, *noise, seed, index_offset, out);
 }
 
 int pdp_vector_sum_metrics(const double* vector_acc, int32_t vector_size, int32_t norm_kind, double max_norm,
@@ -601,12 +575,9 @@ int pdp_vector_sum_metrics(const double* vector_acc, int32_t vector_size, int32_
     return pdp::set_error(PDP_E_INVALID, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = grid_for(n_kept * 64, 2048);  // one wave per kept partition
-  PDP_PROF_BEGIN("k_vector_sum_metrics", st);
-  hipLaunchKernelGGL(k_vector_sum_metrics, dim3(grid), dim3(kBlock), 0, st, vector_acc, (int)vector_size,
-                     (int)norm_kind, max_norm, *noise, index, n_kept, n_kept_dev, partition_offset, out, seed);
-  PDP_PROF_END(st);
-  PDP_HIP_CHECK(hipGetLastError());
-  return PDP_OK;
+  return launch("k_vector_sum_metrics", k_vector_sum_metrics, dim3(grid), dim3(kBlock), 0, st, vector_acc,
+                (int)vector_size, (int)norm_kind, max_norm, *noise, index, n_kept, n_kept_dev, partition_offset, out,
+                seed);
 }
 
 }  // extern "C"

@@ -2,6 +2,8 @@
 fixture parity through UtilityAnalysisEngine.analyze, the kernels' edge shapes
 against the NumPy restatement under the derived tolerances
 (tests/utility_analysis_util.py), and bitwise reproducibility."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -78,6 +80,12 @@ def _edge_configurations(k):
             for i in range(k)]
 
 
+@functools.lru_cache(maxsize=None)
+def _keep_tables():
+    return {l0: E.keep_probability_table(partition_selection.create_partition_selection_strategy(
+        pdp.PartitionSelectionStrategy.TRUNCATED_GEOMETRIC, 1.0, 1e-4, l0)) for l0 in (1, 2, 4, 8)}
+
+
 @pytest.fixture(scope="module")
 def edge():
     import torch
@@ -87,9 +95,7 @@ def edge():
                torch.as_tensor(sm, dtype=torch.float64, device=dev),
                torch.as_tensor(npart, dtype=torch.int64, device=dev))
     by_partition = {p: (cnt[pk == p], sm[pk == p], npart[pk == p]) for p in range(N_PARTITIONS)}
-    tables = {l0: E.keep_probability_table(partition_selection.create_partition_selection_strategy(
-        pdp.PartitionSelectionStrategy.TRUNCATED_GEOMETRIC, 1.0, 1e-4, l0)) for l0 in (1, 2, 4, 8)}
-    return dict(tensors=tensors, pairs=by_partition, tables=tables, restated={})
+    return dict(tensors=tensors, pairs=by_partition, tables=_keep_tables(), restated={})
 
 
 def _run(edge, k, flags=N.UA_SUM | N.UA_COUNT | N.UA_PRIVACY_ID_COUNT, public=False):
@@ -151,6 +157,83 @@ def test_two_runs_are_bitwise_equal(edge):
     _, b = _run(edge, 65)
     for name in ("raw_statistics", "keep_probability", "metrics"):
         assert torch.equal(a[name].view(torch.int64), b[name].view(torch.int64)), name
+
+
+# ---------------------------------------------------- segment split shapes --
+# 300 partitions: 9-bit sort keys, so the radix sort runs two passes.  In sorted
+# order partition 3 (4,096 pairs, one chunk, reduced whole) fills tile 0;
+# partition 4 (4,097 > a chunk) starts exactly on the tile boundary 4,096 and
+# leaves one pair in tile 2; partition 260 (5,000) starts inside that same tile
+# at 8,193, so tile 2 writes both of its partial slots, and ends inside tile 3;
+# partition 299 has 3 pairs.  The other 296 partitions, those between the two
+# long ones included, are empty.
+SPLIT_CODES = (3, 4, 260, 299)
+SPLIT_SIZES = (4096, 4097, 5000, 3)
+SPLIT_PARTITIONS = 300
+SPLIT_K = 65
+
+
+def _split_pairs():
+    rng = np.random.default_rng(11)
+    pk, cnt, sm, npart = [], [], [], []
+    for p, size in zip(SPLIT_CODES, SPLIT_SIZES):
+        pk += [p] * size
+        cnt += [int(v) for v in rng.integers(0, 6, size)]
+        sm += [float(v) for v in rng.integers(-3, 12, size)]
+        npart += [int(2 ** v) for v in rng.integers(0, 5, size)]
+    order = rng.permutation(len(pk))
+    return tuple(np.asarray(a)[order] for a in (pk, cnt, sm, npart))
+
+
+@pytest.fixture(scope="module")
+def split():
+    import torch
+    pk, cnt, sm, npart = _split_pairs()
+    dev = torch.device("cuda:0")
+    tensors = (torch.as_tensor(pk, dtype=torch.int64, device=dev), torch.as_tensor(cnt, dtype=torch.int64, device=dev),
+               torch.as_tensor(sm, dtype=torch.float64, device=dev),
+               torch.as_tensor(npart, dtype=torch.int64, device=dev))
+    by_partition = {p: (cnt[pk == p], sm[pk == p], npart[pk == p]) for p in SPLIT_CODES}
+    return dict(tensors=tensors, pairs=by_partition, tables=_keep_tables(), restated={})
+
+
+def _run_split(split):
+    cfgs = _edge_configurations(SPLIT_K)
+    out = E.run_utility_analysis(*split["tensors"], SPLIT_PARTITIONS,
+                                 [(c["l0"], c["linf"], c["min_sum"], c["max_sum"]) for c in cfgs],
+                                 [split["tables"][c["l0"]] for c in cfgs],
+                                 N.UA_SUM | N.UA_COUNT | N.UA_PRIVACY_ID_COUNT)
+    return cfgs, out
+
+
+def test_segment_split_shapes_against_restatement(split):
+    import torch
+    cfgs, out = _run_split(split)
+    raw = out["raw_statistics"].cpu().numpy()
+    keep = out["keep_probability"].cpu().numpy()
+    metrics = out["metrics"].cpu().numpy()
+    assert metrics.shape == (3, 5, SPLIT_PARTITIONS, SPLIT_K) and keep.shape == (SPLIT_PARTITIONS, SPLIT_K)
+    for p, size in zip(SPLIT_CODES, SPLIT_SIZES):
+        cnt, sm, npart = split["pairs"][p]
+        assert len(cnt) == size and list(raw[p]) == [size, int(cnt.sum())]
+        for c, cfg in enumerate(cfgs):
+            key = (p, c % 60)  # the configurations repeat with period lcm(4, 3, 5)
+            if key not in split["restated"]:
+                vals = [U.restate_metric(m, cnt, sm, npart, cfg)[0] for m in U.METRIC_ORDER]
+                split["restated"][key] = (vals, U.restate_keep(npart, cfg["l0"],
+                                                               U.keep_fn_of_table(split["tables"][cfg["l0"]])))
+            vals, (kv, path, m) = split["restated"][key]
+            for mi in range(3):
+                for fi, f in enumerate(U.FIELDS):  # dyadic inputs: equality
+                    assert metrics[mi, fi, p, c] == vals[mi][f], (p, c, U.METRIC_ORDER[mi], f)
+            bound = U.keep_bound(kv, path, len(npart), m)
+            assert abs(keep[p, c] - kv) <= bound, (p, c, path, keep[p, c], kv, abs(keep[p, c] - kv), bound)
+    empty = np.setdiff1d(np.arange(SPLIT_PARTITIONS), SPLIT_CODES)
+    assert len(empty) == 296
+    assert (raw[empty] == 0).all() and (metrics[:, :, empty, :] == 0).all() and (keep[empty] == 0).all()
+    _, again = _run_split(split)
+    for name in ("raw_statistics", "keep_probability", "metrics"):
+        assert torch.equal(out[name].view(torch.int64), again[name].view(torch.int64)), name
 
 
 def test_out_of_range_partition_is_reported(edge):

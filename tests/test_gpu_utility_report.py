@@ -116,6 +116,8 @@ SHAPES = [
     (list(_mixed_sizes(300, 2)), 5, 1, True),
     (list(_mixed_sizes(9, 3)), 1024, 1, False),
     (list(_mixed_sizes(5, 4)), 1024, 3, True),
+    # three 2,048-partition sort tiles, the last ragged: the key-major count table and the cross-tile bases
+    (list(_mixed_sizes(2 * 2048 + 37, 7)), 3, 1, False),
 ]
 
 
@@ -198,5 +200,13 @@ def test_selection_only():
 def test_two_calls_are_bitwise_equal():
     import torch
     inputs = _inputs(list(_mixed_sizes(3 * TILE + 5, 8)), 130, 3, False, seed=8, absent=[2, 77])
+    a, b = analysis.run_utility_report(*inputs), analysis.run_utility_report(*inputs)
+    assert torch.equal(a[0].view(torch.int64), b[0].view(torch.int64)) and torch.equal(a[1], b[1])
+
+
+def test_two_calls_over_three_sort_tiles_are_bitwise_equal():
+    import torch
+    sizes, K, M, public = SHAPES[-1]
+    inputs = _inputs(sizes, K, M, public, seed=len(SHAPES) - 1, absent=list(range(1, len(sizes), 4)))
     a, b = analysis.run_utility_report(*inputs), analysis.run_utility_report(*inputs)
     assert torch.equal(a[0].view(torch.int64), b[0].view(torch.int64)) and torch.equal(a[1], b[1])

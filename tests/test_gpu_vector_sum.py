@@ -110,6 +110,27 @@ def test_hot_partition_every_row_kept(device):
     assert count.max() > n // 2 and int(count.sum()) == n
 
 
+@pytest.mark.parametrize("d", [3, 16])
+def test_segment_split_shapes(device, d):
+    """NoOp bounding, so the kept-row list is the rows by partition: partition
+    3 (1,024 rows, one tile, summed whole) fills tile 0; partition 4 (1,025)
+    starts exactly on the tile boundary and leaves one row in tile 2; partition
+    30 (1,500) starts inside that same tile, which so writes both of its
+    partial slots, and ends inside tile 3; partition 39 has 3 rows.  d = 3: 8 B
+    lanes in a padded group; d = 16: 16 B lanes."""
+    U, P = 500, 40
+    codes, sizes = (3, 4, 30, 39), (1024, 1025, 1500, 3)
+    rng = np.random.default_rng(40 + d)
+    pk = rng.permutation(np.repeat(codes, sizes)).astype(np.int64)
+    n = len(pk)
+    pid = rng.integers(0, U, n).astype(np.int64)
+    vec = rng.integers(-(1 << 20), (1 << 20) + 1, (n, d)).astype(np.float64)
+    count = _check(device, pid, pk, vec, U=U, P=P, l0=0, linf=0, seed=5)
+    want = np.zeros(P, np.int64)
+    want[list(codes)] = sizes
+    assert (count == want).all()
+
+
 def test_normal_values_within_summation_order(device):
     n, U, P, d = 20000, 3000, 37, 16
     pid, pk, vec = _table(n, U, P, d, seed=6, hot=0.6, integer=False)
