@@ -18,6 +18,13 @@ n_contributions)) rows, and compute_dataset_histograms_on_preaggregated_data
 inconsistent n_partitions pins the weighted bins' rounding (round half to
 even of the summed 1/n_partitions weights, :81-102).
 
+Edge cases (tests/hist_edges_util.py builds the rows): float_edges and its
+pre_ twin hold three value ranges, each dealt out over two or three tables
+(at most two values per bin: every bin sum the same in any order) -- one
+dataset has one pair-sum range, so each file is {"note", "cases": [{"name", "rows", "expected"}, ...]}, which
+tests/hist_util.py unfolds into one fixture per case -- and log_edges the
+privacy ids / partitions with 999 .. 1,010 distinct partners.
+
 Usage: python -m oracle.gen_golden_hist   (from the repo root)
 """
 import json
@@ -99,6 +106,38 @@ def _case(name, rows, note):
     print("wrote", path, len(rows), "rows")
 
 
+def _edge_cases():
+    # by path: once the reference is importable, its own `tests` package shadows this repository's
+    import importlib.util
+    from oracle.gen_golden import ROOT
+    spec = importlib.util.spec_from_file_location("hist_edges_util", os.path.join(ROOT, "tests", "hist_edges_util.py"))
+    E = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(E)
+    raw, pre = [], []
+    for name in E.FIXTURE_RANGES:
+        for j, (pid, pk, val, _, _) in enumerate(E.float_edges(name)):
+            rows = list(zip(pid.tolist(), pk.tolist(), val.tolist()))
+            raw.append({"name": f"{name}.{j}", "rows": [list(r) for r in rows], "expected": _run_reference(rows)})
+            pre_rows = _preaggregate_reference(rows)
+            pre.append({"name": f"{name}.{j}", "rows": [[_py(pk)] + [_py(v) for v in x] for pk, x in pre_rows],
+                        "expected": _run_reference_pre(pre_rows)})
+    mn_mx = {n: [float(v).hex() for v in E.FLOAT_RANGES[n]] for n in E.FIXTURE_RANGES}
+    note = f"hist_edges_util.float_edges: values on and one ulp beside the lowers of linspace(min, max); {mn_mx}"
+    for fname, cases in (("float_edges", raw), ("pre_float_edges", pre)):
+        path = os.path.join(OUT, "histograms", f"dataset_histograms_{fname}.json")
+        with open(path, "w") as f:
+            json.dump({"note": note, "cases": cases}, f, separators=(",", ":"))
+        print("wrote", path, [len(c["rows"]) for c in cases], "rows")
+    pid, pk, val, _, _ = E.log_distinct(E.LOG_DISTINCT_SMALL)
+    rows = list(zip(pid.tolist(), pk.tolist(), val.tolist()))
+    path = os.path.join(OUT, "histograms", "dataset_histograms_log_edges.json")
+    with open(path, "w") as f:
+        json.dump({"note": f"hist_edges_util.log_distinct{E.LOG_DISTINCT_SMALL}: a privacy id with d distinct "
+                           "partitions and a partition with d distinct privacy ids for every d",
+                   "rows": [list(r) for r in rows], "expected": _run_reference(rows)}, f, separators=(",", ":"))
+    print("wrote", path, len(rows), "rows")
+
+
 def main():
     rng = np.random.default_rng(11)
     # 1. random ints, dyadic fp64 values (every sum exact in any order)
@@ -135,6 +174,7 @@ def main():
     pre += [(7, (1, 1.0, 8, 5))] * 3
     pre += [(8 + k, (3, -2.0, 2, 2500)) for k in range(7)]
     _case_pre("weights", pre, "inconsistent n_partitions: non-integer weight sums, round half to even")
+    _edge_cases()
 
 
 if __name__ == "__main__":

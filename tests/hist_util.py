@@ -14,8 +14,10 @@ def _load(pattern, prefix):
     for path in sorted(glob.glob(os.path.join(GOLDEN, pattern))):
         with open(path) as f:
             d = json.load(f)
-        d["name"] = os.path.basename(path)[len(prefix):-len(".json")]
-        out.append(d)
+        name = os.path.basename(path)[len(prefix):-len(".json")]
+        # a file of several datasets ({"cases": [...]}: one value range each) unfolds into one fixture per case
+        for case in d.pop("cases", [None]):
+            out.append(dict(d, name=name) if case is None else {**d, **case, "name": f"{name}/{case['name']}"})
     return out
 
 
