@@ -144,7 +144,9 @@ int64_t per_pid_lds(const pdp_bound_config* c) {
 }
 
 bool test_hooks_enabled();
-Plan make_plan(const pdp_bound_config* c) {
+// The plan with at most 2^max_bucket_bits privacy ids per bucket (make_plan
+// lowers it until the bucket kernel's LDS fits).
+Plan make_plan_capped(const pdp_bound_config* c, int max_bucket_bits) {
   Plan p{};
   p.pk_bits = bits_for(c->n_partitions);
   const int64_t per_pid = per_pid_lds(c);
@@ -164,6 +166,7 @@ Plan make_plan(const pdp_bound_config* c) {
       const char* e = std::getenv("PIPELINEDP_AMD_BUCKET_BITS");
       if (e != nullptr && std::atoi(e) >= 4 && std::atoi(e) < s) s = std::atoi(e);
     }
+    if (s > max_bucket_bits) s = max_bucket_bits;
     const int u_bits = bits_for(c->n_privacy_ids);
     if (s > u_bits) s = u_bits;                          // one bucket covers all pids
     const int64_t nb = (c->n_privacy_ids + ((int64_t)1 << s) - 1) >> s;
@@ -350,6 +353,21 @@ Plan make_plan(const pdp_bound_config* c) {
     p.two_level = 0;
     p.fine_items = 0;
   }
+  return p;
+}
+
+// kLdsBudget bounds the sketches alone; the pid-hash table (8 bytes per id),
+// the wave queues and the range scratch come on top, and the bucket kernel
+// cannot be launched with more than a workgroup's kLdsLimit: 4,096 ids of 28
+// bytes (l0 = 1, linf = 2) or 2,048 of 60 (l0 = 3, linf = 1) went over it.
+// Halve the bucket until the whole of it fits: lds_bytes is the dynamic
+// request, and the kernel's static LDS (kBucketStaticLds) counts as well --
+// 2,048 ids of 60 bytes under the atomic merge come to exactly kLdsLimit
+// without it.
+Plan make_plan(const pdp_bound_config* c) {
+  Plan p = make_plan_capped(c, 63);
+  while (p.algorithm == PDP_ALGO_BUCKETED && p.lds_bytes + kBucketStaticLds > kLdsLimit && p.bucket_bits > 4)
+    p = make_plan_capped(c, p.bucket_bits - 1);
   return p;
 }
 
@@ -2277,6 +2295,12 @@ __device__ __forceinline__ int64_t xcd_major(int64_t id, int64_t G) {
 // FLAT: the per-id fix-up's listed launch (ids over its row cap): blist holds
 // {bucket, begin, end, id}, only that id is marked, and the kept pairs go to
 // the flat list instead of the bucket's record block and runs
+// Static LDS of k_bucket_bound (everything else is its dynamic block).
+struct BucketStatic {
+  unsigned ccount;  // B1's candidate count
+};
+static_assert(sizeof(BucketStatic) <= (size_t)kBucketStaticLds, "make_plan counts kBucketStaticLds bytes of static LDS");
+
 template <int VALUE_KIND, bool KEEP_ALL_ROWS, bool RANGES, int REC, bool FLAT = false>
 __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const RecKey<REC == kRecCompact>* __restrict__ keys,
                                                                  const unsigned* __restrict__ rowidx,
@@ -2295,7 +2319,10 @@ __global__ void __launch_bounds__(kBucketThreads) k_bucket_bound(KP kp, const Re
                                                                  unsigned* __restrict__ id_seg) {
   constexpr bool COMPACT = REC == kRecCompact;
   extern __shared__ unsigned long long smem[];
-  __shared__ unsigned ccount;
+  // the kernel's only static LDS, kept in one struct so that the plan's
+  // allowance for it (kBucketStaticLds, make_plan) is checked where it is declared
+  __shared__ BucketStatic bstat;
+  unsigned& ccount = bstat.ccount;
   const int64_t S = (int64_t)1 << kp.bucket_bits;
   const int l0 = kp.l0;
   // b: the bucket; [begin, end): its records; only_id >= 0 (per-id fix-up,

@@ -31,10 +31,17 @@ constexpr int kL2Runs = kL2GroupTiles * kStagesPerTile;  // level-1 runs per lev
 constexpr int kUnroll = 8;
 constexpr int kBucketThreads = 1024;
 constexpr int64_t kLdsBudget = 124 * 1024;  // per-pid state; + range scratch + wave queues <= 160 KiB
-// 512-thread bucket workgroups: per-pid state <= 56 KiB, so that with the
-// range scratch (<= 4 KiB at 512 ranges), 8 wave queues (12 KiB) and the pid
-// hashes two workgroups fit one CU's 160 KiB
+// 512-thread bucket workgroups: per-pid state <= 56 KiB.  With the range
+// scratch (<= 4 KiB at 512 ranges), 8 wave queues (12 KiB) and the pid hashes
+// (8 bytes per id) two workgroups share one CU's 160 KiB where the ids are
+// few enough (C3: 1,024 ids of 40 bytes, about 64 KiB each); with many small ids
+// (l0 = 1, linf = 2: 2,048 of 28 bytes and 16 KiB of hashes) one workgroup
+// exceeds 80 KiB and runs alone -- make_plan enforces only kLdsLimit
 constexpr int64_t kLdsBudget2 = 56 * 1024;
+// one workgroup's LDS on gfx950: the bucket kernel's dynamic request plus its
+// static LDS (kBucketStaticLds: k_bucket_bound's ccount, with room) stays within it
+constexpr int64_t kLdsLimit = 160 * 1024;
+constexpr int64_t kBucketStaticLds = 64;
 constexpr int kMinRandomBits = 24;
 constexpr int64_t kMaxBuckets = 36 * 1024;  // u32 histogram in 144 KiB of LDS
 constexpr int kMaxSupers = 128;   // destinations of a level-1 scatter
