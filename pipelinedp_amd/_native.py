@@ -218,6 +218,7 @@ HIST_FORCE_PAIR_HASH = 0x200   # tests only: skip the privacy-id buckets
 HIST_SUM_BUCKETS = 10000
 HIST_N_INT = 5
 HIST_N_FLOAT = 2
+HIST_WEIGHT_SMALL = 2000  # dense L0 / L1 weight sums of the pre-aggregated path: 2 * kWSmall (csrc/pdp_hist.hip)
 
 
 class HistogramBins(ctypes.Structure):

@@ -26,12 +26,21 @@
 //               counts and sums are privatised in LDS (120 KB per workgroup);
 //               k_h_float_max, a second pass, its bin maxima (80 KB)
 //   k_h_final   derived sums / maxima of the width-1 bins, fp64 maxima decoded
+// k_h_rows / k_h_pairs are the fallback of the default pairs phase, which
+// hashes the rows into buckets with an LDS pair table each ("bucketed pairs"
+// below: k_hb_count, k_hb_scan_tiles, k_hb_scan_supers, k_hb_l1, k_hb_bcount,
+// k_hb_l2, then k_hb_pid_pairs + k_hb_prange or k_hb_pairs).  Pre-aggregated
+// input has its own kernels ("pre-aggregated input" below: k_hp_rows,
+// k_hp_weights, k_hp_weight_list, k_hp_ids, k_hp_float) and shares k_h_init,
+// k_h_lowers and k_h_final.  The host stages at the end are shared likewise.
 //
 // Integer histograms use the logarithmic bins of
 // _to_bin_lower_upper_logarithmic (:28-47), indexed densely: lower < 1000 ->
 // index = lower (width 1, so bin sum = count * lower and max = lower, which
 // k_h_final fills in: the hot small bins only count, privatised in LDS);
 // lower = q * 10^e (q in [100, 999], e >= 1) -> 1000 + (e - 1) * 900 + q - 100.
+#include <initializer_list>
+
 #include "pdp_internal.h"
 
 namespace pdp {
@@ -133,21 +142,12 @@ constexpr int kHbPidThreads = 1024;
 constexpr int kHbPidSlots = 4032;
 constexpr int kHbPidFill = 3628;         // 90 % of kHbPidSlots
 constexpr int kHbPidPer = (kHbPidSlots + kHbPidThreads - 1) / kHbPidThreads;
-#ifndef PDP_HB_PID_PRE
-#define PDP_HB_PID_PRE 2
-#endif
-constexpr int kHbPidPre = PDP_HB_PID_PRE;  // rows per thread loaded together in k_hb_pid_pairs
+constexpr int kHbPidPre = 2;             // rows per thread loaded together in k_hb_pid_pairs
 constexpr int kHbRangeBits = 11;
 constexpr int kHbRangeW = 1 << kHbRangeBits;
 constexpr int kHbRangeMax = 128;         // more ranges (P > 262,144): per-pair partition atomics
 constexpr int kHbRangeThreads = 1024;
-#ifndef PDP_HB_RANGE_U
-#define PDP_HB_RANGE_U 4
-#endif
-constexpr int kHbRangeU = PDP_HB_RANGE_U;
-#ifndef PDP_HB_RANGE_WAVE
-#define PDP_HB_RANGE_WAVE 1  // k_hb_prange: one wave per 64 buckets' runs (else a workgroup scan + search per record)
-#endif  // records per thread in flight in k_hb_prange
+constexpr int kHbRangeU = 4;             // runs per wave in flight in k_hb_prange (one record per lane each)
 static_assert(kHbPidSlots * 12 + kSmallBins * 4 + 3 * (kHbRangeMax + 1) * 4 <= kHbPidSlots * 20,
               "the pid table, Linf bins and range counters reuse the pair table's LDS");
 
@@ -387,9 +387,22 @@ __global__ void __launch_bounds__(kBlock) k_h_rows(HT t, const int64_t* __restri
   }
 }
 
-// block-wide min/max of ordered fp64 images, one atomic pair per block
-__device__ __forceinline__ void block_minmax(unsigned long long mn, unsigned long long mx, unsigned long long* out) {
+// a thread's running min / max of fp64 values as ordered images (every kernel
+// that feeds the float histograms' ranges: k_h_pairs, k_h_ids, k_hb_pairs,
+// k_hb_pid_pairs, k_hb_prange, k_hp_rows, k_hp_ids)
+struct OrdRange {
+  unsigned long long mn = ~0ULL, mx = 0ULL;
+  __device__ __forceinline__ void add(unsigned long long o) {
+    mn = o < mn ? o : mn;
+    mx = o > mx ? o : mx;
+  }
+  __device__ __forceinline__ void add(double x) { add(ord(x)); }
+};
+
+// block-wide min/max of the threads' ranges, one atomic pair per block
+__device__ __forceinline__ void block_minmax(const OrdRange& range, unsigned long long* out) {
   __shared__ unsigned long long smn[16], smx[16];
+  unsigned long long mn = range.mn, mx = range.mx;
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
     mn = a < mn ? a : mn;
@@ -433,7 +446,7 @@ __global__ void __launch_bounds__(kPairsBlock) k_h_pairs(HT t, const Slot* __res
     r_first = lo;
   }
   __syncthreads();
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
   for (int64_t r = r_first; s0 < s1 && r < t.R && (int64_t)rbase[r] < s1; ++r) {
     const int64_t a = (int64_t)rbase[r] > s0 ? (int64_t)rbase[r] : s0;
     const int64_t e = (int64_t)rbase[r + 1] < s1 ? (int64_t)rbase[r + 1] : s1;
@@ -454,9 +467,7 @@ __global__ void __launch_bounds__(kPairsBlock) k_h_pairs(HT t, const Slot* __res
       atomicAdd(lstat + j, inc);
       if (t.has_value) atomicAdd(lsum + j, sl.sum);
       int_hist_add(H, lds, H_LINF, 0, rows);
-      const unsigned long long o = ord(sl.sum);
-      mn = o < mn ? o : mn;
-      mx = o > mx ? o : mx;
+      range.add(sl.sum);
     }
     __syncthreads();
     const int64_t p0 = r << kRegionBits;
@@ -469,7 +480,7 @@ __global__ void __launch_bounds__(kPairsBlock) k_h_pairs(HT t, const Slot* __res
     }
     __syncthreads();
   }
-  block_minmax(mn, mx, minmax);  // contains __syncthreads: every thread reaches it
+  block_minmax(range, minmax);  // contains __syncthreads: every thread reaches it
   __syncthreads();
   flush_small(H, lds, 0, H_LINF);
 }
@@ -484,7 +495,7 @@ __global__ void __launch_bounds__(kIdsThreads) k_h_ids(HT t, const unsigned long
   __syncthreads();
   const int64_t m = t.U > t.P ? t.U : t.P;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
   // the loop bound is workgroup-uniform, so every wave stays converged for
   // int_hist_add_wave; lanes past the end carry no element
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < m; i0 += stride) {
@@ -499,14 +510,10 @@ __global__ void __launch_bounds__(kIdsThreads) k_h_ids(HT t, const unsigned long
     if (t.do_parts) {
       int_hist_add_wave(H, lds, H_COUNT, 2, sp & 0xFFFFFFFFULL, sp != 0);
       int_hist_add_wave(H, lds, H_PIDS, 3, sp >> 32, sp != 0);
-      if (sp) {
-        const unsigned long long o = ord(ps);
-        mn = o < mn ? o : mn;
-        mx = o > mx ? o : mx;
-      }
+      if (sp) range.add(ps);
     }
   }
-  block_minmax(mn, mx, minmax + 2);
+  block_minmax(range, minmax + 2);
   __syncthreads();
   flush_small(H, lds, 0, H_L0);
   flush_small(H, lds, 1, H_L1);
@@ -617,10 +624,8 @@ __device__ __forceinline__ void max_filtered(unsigned long long* omax, unsigned 
 }
 
 constexpr int kFloatBlock = 1024;
-#ifndef PDP_HF_U
-#define PDP_HF_U 8
-#endif
-constexpr int kFloatU = PDP_HF_U;  // pair sums in flight per thread
+constexpr int kFloatU = 8;       // pair sums in flight per thread
+constexpr int kFloatMaxOcc = 4;  // k_h_float_max: waves per SIMD asked of the compiler
 
 // every pair sum of the call's pair phase, in the form it left them: the pair
 // buckets' list (mode 1), the privacy-id buckets' range-grouped records
@@ -684,11 +689,8 @@ __device__ __forceinline__ void for_pair_sums(const HT& t, const Slot* __restric
 // atomicMax -- at ~4 raises per bin and workgroup those atomics, waited on by
 // the next loads (one in-order vmcnt), took 1.0 of its 1.7 ms
 // (profiles/r05/ab/ab10_hist_latency.txt); the second pass re-reads 1.6 GB.
-#ifndef PDP_HF_MAXOCC
-#define PDP_HF_MAXOCC 4
-#endif
 template <bool MAX>
-__global__ void __launch_bounds__(kFloatBlock, MAX ? PDP_HF_MAXOCC : 4) k_h_float(HT t, const Slot* __restrict__ slots,
+__global__ void __launch_bounds__(kFloatBlock, MAX ? kFloatMaxOcc : 4) k_h_float(HT t, const Slot* __restrict__ slots,
                                                          const double* __restrict__ pairsum,
                                                          const unsigned* __restrict__ hb_ctl,
                                                          const unsigned* __restrict__ hb_bstart,
@@ -785,23 +787,41 @@ __device__ __forceinline__ unsigned hb_bucket_t(const HT& t, unsigned long long 
   return hb_bucket(t.hb_pid ? x >> t.pk_bits : x, t.nb);
 }
 
+// inclusive scan of one u32 per lane over a whole, converged wave
+// (hb_block_scan, wave_counts_to_starts)
+__device__ __forceinline__ unsigned wave_inclusive_scan(unsigned x) {
+  const int lane = threadIdx.x & 63;
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  return x;
+}
+
+// wave 0, all of its lanes: the n counts in LDS -> their exclusive starts, 64
+// at a time with a carry; returns the total (the counting sorts of k_hb_l1 and
+// k_hb_l2, the range counts of k_hb_pid_pairs)
+__device__ __forceinline__ unsigned wave_counts_to_starts(const unsigned* cnt, unsigned* start, int n) {
+  const int lane = threadIdx.x;
+  unsigned carry = 0;
+  for (int b0 = 0; b0 < n; b0 += 64) {
+    const unsigned c = b0 + lane < n ? cnt[b0 + lane] : 0u;
+    const unsigned incl = wave_inclusive_scan(c);
+    if (b0 + lane < n) start[b0 + lane] = carry + incl - c;
+    carry += __shfl(incl, 63, 64);
+  }
+  return carry;
+}
+
 // exclusive scan of one u32 per thread over the workgroup (wsum: nw + 1 words)
 __device__ __forceinline__ unsigned hb_block_scan(unsigned x, unsigned* wsum, unsigned* total) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  unsigned inc = x;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned y = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += y;
-  }
+  const unsigned inc = wave_inclusive_scan(x);
   if (lane == 63) wsum[w] = inc;
   __syncthreads();
   if (w == 0) {
     const unsigned v = lane < nw ? wsum[lane] : 0;
-    unsigned vi = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned y = __shfl_up(vi, off, 64);
-      if (lane >= off) vi += y;
-    }
+    const unsigned vi = wave_inclusive_scan(v);
     if (lane < nw) wsum[lane] = vi - v;
     if (lane == nw - 1) wsum[nw] = vi;
   }
@@ -811,6 +831,31 @@ __device__ __forceinline__ unsigned hb_block_scan(unsigned x, unsigned* wsum, un
   __syncthreads();
   return r;
 }
+
+// one LDS stage of a partition level's counting sort (k_hb_l1, k_hb_l2): the
+// stage's records sorted by destination, start[d] the first slot of d's
+template <bool HAS_VALUE>
+struct HbStage {
+  unsigned long long* key;
+  double* val;
+  uint8_t* dest;
+  const unsigned* start;
+  // record (x, v), the rank-th of destination d's, into its slot
+  __device__ __forceinline__ void place(int d, unsigned rank, unsigned long long x, double v) const {
+    const unsigned slot = start[d] + rank;
+    key[slot] = x;
+    if (HAS_VALUE) val[slot] = v;
+    dest[slot] = (uint8_t)d;
+  }
+  // sorted record e out to cursor[its destination] + its place in the run
+  __device__ __forceinline__ void write_out(unsigned e, const unsigned* cursor, unsigned long long* okey,
+                                            double* oval) const {
+    const unsigned dd = dest[e];
+    const unsigned g = cursor[dd] + (e - start[dd]);
+    okey[g] = key[e];
+    if (HAS_VALUE) oval[g] = val[e];
+  }
+};
 
 // step 1: valid rows per (tile, super-bucket); invalid keys set the error word
 __global__ void __launch_bounds__(kHbThreads) k_hb_count(HT t, const int64_t* __restrict__ pid,
@@ -890,6 +935,7 @@ __global__ void __launch_bounds__(kHbThreads) k_hb_l1(HT t, const int64_t* __res
   unsigned* start = hist + kHbFan;                         // [kHbFan]
   unsigned* cur = start + kHbFan;                          // [kHbFan]: the tile's output cursor per super
   uint8_t* dest = (uint8_t*)(cur + kHbFan);                // [kHbStage]
+  const HbStage<VK != PDP_VALUE_NONE> stage{skey, sval, dest, start};
   constexpr int N = kHbStage / kHbThreads;
   const int64_t t0 = (int64_t)blockIdx.x * kHbTileRows;
   const int64_t t1 = t0 + kHbTileRows < t.n ? t0 + kHbTileRows : t.n;
@@ -936,37 +982,14 @@ __global__ void __launch_bounds__(kHbThreads) k_hb_l1(HT t, const int64_t* __res
 #pragma unroll
     for (int q = 0; q < N; ++q) rank[q] = d[q] >= 0 ? atomicAdd(hist + d[q], 1u) : 0u;
     __syncthreads();
-    if (threadIdx.x < 64) {  // exclusive scan of hist by one wave
-      const int lane = threadIdx.x;
-      unsigned carry = 0;
-      for (int base = 0; base < t.n_supers; base += 64) {
-        const unsigned hv = base + lane < t.n_supers ? hist[base + lane] : 0u;
-        unsigned incl = hv;
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned up = __shfl_up(incl, off, 64);
-          if (lane >= off) incl += up;
-        }
-        if (base + lane < t.n_supers) start[base + lane] = carry + incl - hv;
-        carry += __shfl(incl, 63, 64);
-      }
-    }
+    if (threadIdx.x < 64) wave_counts_to_starts(hist, start, (int)t.n_supers);
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < N; ++q) {
-      if (d[q] < 0) continue;
-      const unsigned slot = start[d[q]] + rank[q];
-      skey[slot] = x[q];
-      if (VK != PDP_VALUE_NONE) sval[slot] = v[q];
-      dest[slot] = (uint8_t)d[q];
-    }
+    for (int q = 0; q < N; ++q)
+      if (d[q] >= 0) stage.place(d[q], rank[q], x[q], v[q]);
     __syncthreads();
     const unsigned total = t.n_supers > 0 ? start[t.n_supers - 1] + hist[t.n_supers - 1] : 0u;
-    for (unsigned e = threadIdx.x; e < total; e += blockDim.x) {
-      const unsigned dd = dest[e];
-      const unsigned g = cur[dd] + (e - start[dd]);
-      okey[g] = skey[e];
-      if (VK != PDP_VALUE_NONE) oval[g] = sval[e];
-    }
+    for (unsigned e = threadIdx.x; e < total; e += blockDim.x) stage.write_out(e, cur, okey, oval);
     __syncthreads();
     for (int b = threadIdx.x; b < t.n_supers; b += blockDim.x) cur[b] += hist[b];
   }
@@ -1020,6 +1043,7 @@ __global__ void __launch_bounds__(kHbL2Threads) k_hb_l2(HT t, const unsigned* __
   __shared__ double sval[HAS_VALUE ? kHbWin : 1];
   __shared__ uint8_t dest[kHbWin];
   __shared__ unsigned hist[kHbFan], start[kHbFan], base[kHbFan];
+  const HbStage<HAS_VALUE> stage{skey, sval, dest, start};
   constexpr int N = kHbWin / kHbL2Threads;
   const int s = blockIdx.x / kHbK, k = blockIdx.x % kHbK;
   const int64_t a = sbase[s], e = sbase[s + 1];
@@ -1049,20 +1073,7 @@ __global__ void __launch_bounds__(kHbL2Threads) k_hb_l2(HT t, const unsigned* __
 #pragma unroll
     for (int q = 0; q < N; ++q) rank[q] = d[q] >= 0 ? atomicAdd(hist + d[q], 1u) : 0u;
     __syncthreads();
-    if (threadIdx.x < 64) {
-      const int lane = threadIdx.x;
-      unsigned carry = 0;
-      for (int b0 = 0; b0 < kHbFan; b0 += 64) {
-        const unsigned hv = hist[b0 + lane];
-        unsigned incl = hv;
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned up = __shfl_up(incl, off, 64);
-          if (lane >= off) incl += up;
-        }
-        start[b0 + lane] = carry + incl - hv;
-        carry += __shfl(incl, 63, 64);
-      }
-    }
+    if (threadIdx.x < 64) wave_counts_to_starts(hist, start, kHbFan);
     // one cursor reservation per non-empty run of this window
     for (int b = threadIdx.x; b < kHbFan; b += blockDim.x) {
       const int64_t g = (int64_t)s * kHbFan + b;
@@ -1070,22 +1081,34 @@ __global__ void __launch_bounds__(kHbL2Threads) k_hb_l2(HT t, const unsigned* __
     }
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < N; ++q) {
-      if (d[q] < 0) continue;
-      const unsigned slot = start[d[q]] + rank[q];
-      skey[slot] = x[q];
-      if (HAS_VALUE) sval[slot] = v[q];
-      dest[slot] = (uint8_t)d[q];
-    }
+    for (int q = 0; q < N; ++q)
+      if (d[q] >= 0) stage.place(d[q], rank[q], x[q], v[q]);
     __syncthreads();
     const unsigned total = (unsigned)(w1 - w0);
-    for (unsigned i = threadIdx.x; i < total; i += blockDim.x) {
-      const unsigned dd = dest[i];
-      const unsigned g = base[dd] + (i - start[dd]);
-      okey[g] = skey[i];
-      if (HAS_VALUE) oval[g] = sval[i];
-    }
+    for (unsigned i = threadIdx.x; i < total; i += blockDim.x) stage.write_out(i, base, okey, oval);
     __syncthreads();
+  }
+}
+
+// find-or-insert of pair key x in an LDS table of SLOTS keys (~0 = empty,
+// linear probing): x's slot, or ~0u once the table holds `limit` keys.  New
+// keys are counted in *fill only when count_fill (k_hb_pairs: always;
+// k_hb_pid_pairs: only a bucket with more rows than the limit)
+template <int SLOTS>
+__device__ __forceinline__ unsigned hb_pair_slot(unsigned long long* tkey, unsigned* fill, unsigned long long x,
+                                                 int limit, bool count_fill) {
+  unsigned sl = (unsigned)(((mix64(x) & 0xFFFFFFFFULL) * (uint64_t)SLOTS) >> 32);
+  for (;;) {
+    const unsigned long long cur = tkey[sl];
+    if (cur == x) return sl;
+    if (cur == ~0ULL) {
+      if (count_fill && atomicAdd(fill, 1u) >= (unsigned)limit) return ~0u;  // table too full: fall back
+      const unsigned long long old = atomicCAS(tkey + sl, ~0ULL, x);
+      if (old == ~0ULL) return sl;
+      if (count_fill) atomicSub(fill, 1u);  // lost the slot to another key
+      if (old == x) return sl;
+    }
+    sl = sl + 1 == (unsigned)SLOTS ? 0u : sl + 1;
   }
 }
 
@@ -1118,24 +1141,11 @@ __global__ void __launch_bounds__(kHbPairThreads) k_hb_pairs(HT t, const unsigne
   const int64_t a = bstart[blockIdx.x], e = bstart[blockIdx.x + 1];
   bool over = false;
   for (int64_t i = a + threadIdx.x; i < e; i += blockDim.x) {
-    const unsigned long long x = key[i];
-    unsigned sl = (unsigned)(((mix64(x) & 0xFFFFFFFFULL) * (uint64_t)kHbSlots) >> 32);
-    for (;;) {
-      const unsigned long long cur = tkey[sl];
-      if (cur == x) break;
-      if (cur == ~0ULL) {
-        if (atomicAdd(&fill, 1u) >= (unsigned)kHbFill) {  // table too full: fall back
-          over = true;
-          break;
-        }
-        const unsigned long long old = atomicCAS(tkey + sl, ~0ULL, x);
-        if (old == ~0ULL) break;
-        atomicSub(&fill, 1u);  // lost the slot to another key
-        if (old == x) break;
-      }
-      sl = sl + 1 == (unsigned)kHbSlots ? 0u : sl + 1;
+    const unsigned sl = hb_pair_slot<kHbSlots>(tkey, &fill, key[i], kHbFill, true);
+    if (sl == ~0u) {
+      over = true;
+      break;
     }
-    if (over) break;
     atomicAdd(tcnt + sl, 1u);
     if (HAS_VALUE) atomicAdd(tsum + sl, val[i]);
   }
@@ -1146,7 +1156,7 @@ __global__ void __launch_bounds__(kHbPairThreads) k_hb_pairs(HT t, const unsigne
     fill = 0;
   }
   __syncthreads();
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
   for (int j = threadIdx.x; j < kHbSlots; j += blockDim.x) {
     const unsigned long long x = tkey[j];
     const unsigned rows = tcnt[j];
@@ -1158,13 +1168,11 @@ __global__ void __launch_bounds__(kHbPairThreads) k_hb_pairs(HT t, const unsigne
     atomicAdd(pkstat + p, inc);
     if (HAS_VALUE) atomicAdd(psum + p, sum);
     int_hist_add(H, lds, H_LINF, 0, rows);
-    const unsigned long long o = ord(sum);
-    mn = o < mn ? o : mn;
-    mx = o > mx ? o : mx;
+    range.add(sum);
     const unsigned long long at = (unsigned long long)s_base + atomicAdd(&fill, 1u);
     if (at < (unsigned long long)t.n) pairsum[at] = sum;  // (an overflowed call is discarded)
   }
-  block_minmax(mn, mx, minmax);  // contains __syncthreads
+  block_minmax(range, minmax);  // contains __syncthreads
   __syncthreads();
   flush_small(H, lds, 0, H_LINF);
 }
@@ -1234,24 +1242,11 @@ __global__ void __launch_bounds__(kHbPidThreads) k_hb_pid_pairs(
 #pragma unroll
     for (int q = 0; q < kHbPidPre; ++q) {
       if (over || i0 + (int64_t)q * blockDim.x >= e) break;
-      const unsigned long long x = xs[q];
-      unsigned sl = (unsigned)(((mix64(x) & 0xFFFFFFFFULL) * (uint64_t)kHbPidSlots) >> 32);
-      for (;;) {
-        const unsigned long long cur = tkey[sl];
-        if (cur == x) break;
-        if (cur == ~0ULL) {
-          if (may_over && atomicAdd(&fill, 1u) >= (unsigned)kHbPidFill) {
-            over = true;
-            break;
-          }
-          const unsigned long long old = atomicCAS(tkey + sl, ~0ULL, x);
-          if (old == ~0ULL) break;
-          if (may_over) atomicSub(&fill, 1u);
-          if (old == x) break;
-        }
-        sl = sl + 1 == (unsigned)kHbPidSlots ? 0u : sl + 1;
+      const unsigned sl = hb_pair_slot<kHbPidSlots>(tkey, &fill, xs[q], kHbPidFill, may_over);
+      if (sl == ~0u) {
+        over = true;
+        break;
       }
-      if (over) break;
       atomicAdd(tcnt + sl, 1u);
       if (HAS_VALUE) atomicAdd(tsum + sl, vs[q]);
     }
@@ -1292,7 +1287,7 @@ __global__ void __launch_bounds__(kHbPidThreads) k_hb_pid_pairs(
     for (int i = threadIdx.x; i <= kHbRangeMax; i += blockDim.x) rcnt[i] = 0;
   if (threadIdx.x == 0) fill = 0;
   __syncthreads();
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
 #pragma unroll
   for (int q = 0; q < kHbPidPer; ++q) {
     rk[q] = 0;
@@ -1316,9 +1311,7 @@ __global__ void __launch_bounds__(kHbPidThreads) k_hb_pid_pairs(
       rk[q] = atomicAdd(rcnt + (p >> kHbRangeBits), 1u);
     } else {
       int_hist_add(H, lbins, H_LINF, 0, kc[q]);
-      const unsigned long long o = ord(ks[q]);
-      mn = o < mn ? o : mn;
-      mx = o > mx ? o : mx;
+      range.add(ks[q]);
       pp[q] = atomicAdd(&fill, 1u);
       atomicAdd(pkstat + p, (1ULL << 32) | kc[q]);
       if (HAS_VALUE) atomicAdd(psum + p, ks[q]);
@@ -1327,20 +1320,9 @@ __global__ void __launch_bounds__(kHbPidThreads) k_hb_pid_pairs(
   __syncthreads();
   const int R = (int)t.hb_R;
   if (threadIdx.x < 64) {
-    if (RANGES) {  // exclusive scan of the range counts by one wave
-      const int lane = threadIdx.x;
-      unsigned carry = 0;
-      for (int b0 = 0; b0 < R; b0 += 64) {
-        const unsigned hv = b0 + lane < R ? rcnt[b0 + lane] : 0u;
-        unsigned incl = hv;
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned up = __shfl_up(incl, off, 64);
-          if (lane >= off) incl += up;
-        }
-        if (b0 + lane < R) rstart[b0 + lane] = carry + incl - hv;
-        carry += __shfl(incl, 63, 64);
-      }
-      if (lane == 0) rstart[R] = carry;
+    if (RANGES) {
+      const unsigned pairs = wave_counts_to_starts(rcnt, rstart, R);
+      if (threadIdx.x == 0) rstart[R] = pairs;
     }
     if (!RANGES && threadIdx.x == 0) s_base = atomicAdd(ctl + 1, fill);  // this bucket's pair sums
   }
@@ -1370,7 +1352,7 @@ __global__ void __launch_bounds__(kHbPidThreads) k_hb_pid_pairs(
     for (int64_t j = a + rstart[R] + threadIdx.x; j < e; j += blockDim.x) prec[j].pk = ~0u;
   if (!RANGES) {
     flush_small(H, lbins, 0, H_LINF);
-    block_minmax(mn, mx, minmax);  // contains __syncthreads (workgroup-uniform branch)
+    block_minmax(range, minmax);  // contains __syncthreads (workgroup-uniform branch)
   }
 }
 
@@ -1380,9 +1362,7 @@ size_t hb_pid_lds() { return (size_t)kHbPidSlots * 20; }
 // of partition range r over buckets [g * per, (g + 1) * per) in LDS -- per
 // partition distinct pids, rows and value sum -- and flushes each partition
 // with one packed atomic (+ one for the sum); each record is one pair, so its
-// rows go to the Linf bins (LDS) and its sum to the pair-sum range.  A chunk
-// of 1,024 buckets' runs is flattened by a workgroup scan, so every lane
-// reads a record of the same runs (contiguous within a run).
+// rows go to the Linf bins (LDS) and its sum to the pair-sum range.
 template <bool HAS_VALUE>
 __global__ void __launch_bounds__(kHbRangeThreads) k_hb_prange(HT t, const unsigned* __restrict__ bstart,
                                                                const unsigned* __restrict__ pruns,
@@ -1392,8 +1372,6 @@ __global__ void __launch_bounds__(kHbRangeThreads) k_hb_prange(HT t, const unsig
   __shared__ unsigned an[kHbRangeW], ar[kHbRangeW];
   __shared__ unsigned lbins[kSmallBins];
   __shared__ double as[HAS_VALUE ? kHbRangeW : 1];
-  __shared__ unsigned bex[kHbRangeThreads], bbase[kHbRangeThreads];
-  __shared__ unsigned wsum[kHbRangeThreads / 64 + 1];
   const int64_t r = blockIdx.x, R = t.hb_R;
   for (int p = threadIdx.x; p < kHbRangeW; p += blockDim.x) {
     an[p] = 0;
@@ -1401,7 +1379,7 @@ __global__ void __launch_bounds__(kHbRangeThreads) k_hb_prange(HT t, const unsig
     if (HAS_VALUE) as[p] = 0.0;
   }
   for (int i = threadIdx.x; i < kSmallBins; i += blockDim.x) lbins[i] = 0;
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
   const int64_t b0 = (int64_t)blockIdx.y * per;
   const int64_t b1 = b0 + per < t.nb ? b0 + per : t.nb;
   auto add = [&](const PRec& rec) {
@@ -1416,11 +1394,8 @@ __global__ void __launch_bounds__(kHbRangeThreads) k_hb_prange(HT t, const unsig
     const unsigned long long same = __ballot(rec.rows == r0);
     if (rec.rows != r0) int_hist_add(H, lbins, H_LINF, 0, rec.rows);
     else if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1) int_hist_add_n(H, lbins, H_LINF, 0, r0, __popcll(same));
-    const unsigned long long o = ord(rec.sum);
-    mn = o < mn ? o : mn;
-    mx = o > mx ? o : mx;
+    range.add(rec.sum);
   };
-#if PDP_HB_RANGE_WAVE
   // each wave takes 64 buckets' runs of range r: lane i loads bucket i's run
   // bounds (one latency round), then the wave reads kHbRangeU runs at a time,
   // one record per lane (a run averages a few dozen records), loads
@@ -1458,48 +1433,7 @@ __global__ void __launch_bounds__(kHbRangeThreads) k_hb_prange(HT t, const unsig
     }
   }
   __syncthreads();
-#else
-  for (int64_t c0 = b0; c0 < b1; c0 += kHbRangeThreads) {  // workgroup-uniform
-    const int64_t b = c0 + threadIdx.x;
-    unsigned len = 0, base = 0;
-    if (b < b1) {
-      const unsigned s = pruns[b * (R + 1) + r], s1 = pruns[b * (R + 1) + r + 1];
-      const unsigned rows = bstart[b + 1] - bstart[b];
-      if (s <= s1 && s1 <= rows) {  // a bucket's records lie inside its rows
-        base = bstart[b] + s;
-        len = s1 - s;
-      }
-    }
-    unsigned tot;
-    const unsigned ex = hb_block_scan(len, wsum, &tot);  // its barriers also order the LDS clears
-    bex[threadIdx.x] = ex;
-    bbase[threadIdx.x] = base;
-    __syncthreads();
-    // kHbRangeU records per thread in flight (one memory latency per batch)
-    for (unsigned f0 = threadIdx.x; f0 < tot; f0 += kHbRangeU * blockDim.x) {
-      PRec recs[kHbRangeU];
-#pragma unroll
-      for (int u = 0; u < kHbRangeU; ++u) {
-        const unsigned f = f0 + u * blockDim.x;
-        if (f >= tot) break;
-        int lo = 0, hi = kHbRangeThreads;  // the last run starting at or before f
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if (bex[mid] <= f) lo = mid;
-          else hi = mid;
-        }
-        recs[u] = prec[bbase[lo] + (f - bex[lo])];
-      }
-#pragma unroll
-      for (int u = 0; u < kHbRangeU; ++u) {
-        if (f0 + u * blockDim.x >= tot) break;
-        add(recs[u]);
-      }
-    }
-    __syncthreads();
-  }
-#endif
-  block_minmax(mn, mx, minmax);  // contains __syncthreads
+  block_minmax(range, minmax);  // contains __syncthreads
   __syncthreads();
   flush_small(H, lbins, 0, H_LINF);
   for (int p = threadIdx.x; p < kHbRangeW; p += blockDim.x) {
@@ -1600,7 +1534,7 @@ __global__ void __launch_bounds__(kBlock) k_hp_rows(PT t, const int64_t* __restr
   for (int b = threadIdx.x; b < 2 * kWSmall; b += blockDim.x) lw[b] = 0.0;
   __syncthreads();
   constexpr int64_t kMaxV = (int64_t)1 << 62;
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
     const int64_t p = pk[i], c = count[i], np = npart[i], nc = ncontr[i];
@@ -1617,14 +1551,12 @@ __global__ void __launch_bounds__(kBlock) k_hp_rows(PT t, const int64_t* __restr
     atomicAdd(pkrows + p, 1ULL);
     atomicAdd(pkcount + p, (unsigned long long)c);
     atomicAdd(psum + p, s);
-    const unsigned long long o = ord(s);
-    mn = o < mn ? o : mn;
-    mx = o > mx ? o : mx;
+    range.add(s);
     const double w = __ddiv_rn(1.0, (double)np);  // 1.0 / x[2] (:536-541, :560-565)
     weight_add(lw, wtab, t.cap, H_L0, (uint64_t)np, w);
     weight_add(lw, wtab, t.cap, H_L1, (uint64_t)nc, w);
   }
-  block_minmax(mn, mx, minmax);  // contains __syncthreads: every thread reaches it
+  block_minmax(range, minmax);  // contains __syncthreads: every thread reaches it
   __syncthreads();
   flush_small(H, lcnt, 0, H_LINF);
   for (int b = threadIdx.x; b < 2 * kWSmall; b += blockDim.x)
@@ -1692,17 +1624,15 @@ __global__ void __launch_bounds__(kBlock) k_hp_ids(PT t, const unsigned long lon
   for (int b = threadIdx.x; b < 2 * kSmallBins; b += blockDim.x) lds[b] = 0;
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  unsigned long long mn = ~0ULL, mx = 0ULL;
+  OrdRange range;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.P; i += stride) {
     const unsigned long long r = pkrows[i];
     if (r == 0) continue;
     int_hist_add(H, lds, H_COUNT, 0, pkcount[i]);
     int_hist_add(H, lds, H_PIDS, 1, r);
-    const unsigned long long o = ord(psum[i]);
-    mn = o < mn ? o : mn;
-    mx = o > mx ? o : mx;
+    range.add(psum[i]);
   }
-  block_minmax(mn, mx, minmax + 2);
+  block_minmax(range, minmax + 2);
   __syncthreads();
   flush_small(H, lds, 0, H_COUNT);
   flush_small(H, lds, 1, H_PIDS);
@@ -1753,52 +1683,102 @@ __global__ void __launch_bounds__(kFloatBlock) k_hp_float(PT t, const double* __
   }
 }
 
-}  // namespace
-}  // namespace pdp
-
-extern "C" {
-
-int pdp_dataset_histograms_workspace_bytes(int64_t n_rows, int64_t n_privacy_ids, int64_t n_partitions,
-                                           uint64_t* bytes) {
-  if (bytes == nullptr) return pdp::set_error(PDP_E_INVALID, "NULL argument");
-  if (n_rows < 0 || n_privacy_ids < 0 || n_partitions < 0)
-    return pdp::set_error(PDP_E_INVALID, "sizes must be >= 0");
-  *bytes = pdp::hlayout(n_rows, n_privacy_ids, n_partitions).total;
+// ------------------------------------------------------------ host stages --
+// an entry point's arguments: every listed pointer set, no size negative
+int sizes_check(std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> sizes) {
+  for (const void* p : ptrs)
+    if (p == nullptr) return set_error(PDP_E_INVALID, "NULL argument");
+  for (const int64_t s : sizes)
+    if (s < 0) return set_error(PDP_E_INVALID, "sizes must be >= 0");
   return PDP_OK;
 }
 
-}  // extern "C"
-
-namespace pdp {
-namespace {
-
-struct HCall {
-  HWs w;
-  HT t;
+// what a raw and a pre-aggregated call share: the workspace, the stream and
+// the caller's bins, as given and as the kernels take them
+struct Call {
   char* ws;
   hipStream_t st;
+  const pdp_histogram_bins* out;
   IntHists H;
-  FloatHists F;
+  FloatHists F;  // omax: ordered images in the workspace (call_workspace)
+};
+
+// the caller's bins, every one set (ints_only: the integer ones)
+int bins_check(const pdp_histogram_bins* out, bool ints_only, Call* c) {
+  const bool ints = out != nullptr && out->int_count != nullptr && out->int_sum != nullptr && out->int_max != nullptr;
+  if (ints_only && !ints) return set_error(PDP_E_INVALID, "the integer pdp_histogram_bins outputs must be set");
+  if (!ints_only && (!ints || out->float_count == nullptr || out->float_sum == nullptr || out->float_max == nullptr ||
+                     out->float_lowers == nullptr || out->float_n_lowers == nullptr))
+    return set_error(PDP_E_INVALID, "every pdp_histogram_bins output must be set");
+  c->out = out;
+  c->H = IntHists{(unsigned long long*)out->int_count, (unsigned long long*)out->int_sum,
+                  (unsigned long long*)out->int_max};
+  c->F = FloatHists{(unsigned long long*)out->float_count, out->float_sum, nullptr};
+  return PDP_OK;
+}
+
+// the bins, the sizes and the row limit of a call, then (its layout known)
+// its workspace of `total` bytes with the float maxima's images at `fmax`
+int call_check(const pdp_histogram_bins* out, std::initializer_list<int64_t> sizes, int64_t n_rows, Call* c) {
+  if (int rc = bins_check(out, false, c); rc != PDP_OK) return rc;
+  if (int rc = sizes_check({}, sizes); rc != PDP_OK) return rc;
+  if (n_rows >= (int64_t)1 << 31) return set_error(PDP_E_UNSUPPORTED, "n_rows must be < 2^31 per shard");
+  return PDP_OK;
+}
+int call_workspace(void* workspace, uint64_t workspace_bytes, uint64_t total, uint64_t fmax, const char* too_small,
+                   void* stream, Call* c) {
+  if (workspace == nullptr || workspace_bytes < total) return set_error(PDP_E_INVALID, too_small);
+  c->ws = (char*)workspace;
+  c->st = (hipStream_t)stream;
+  c->F.omax = (unsigned long long*)(c->ws + fmax);
+  return PDP_OK;
+}
+
+// the caller's bins zeroed: the integer ones, with `floats` the float ones too
+int zero_outputs(const Call& c, bool floats) {
+  for (void* p : {c.out->int_count, c.out->int_sum, c.out->int_max})
+    PDP_HIP_CHECK(hipMemsetAsync(p, 0, 5 * kLogBins * 8, c.st));
+  if (!floats) return PDP_OK;
+  PDP_HIP_CHECK(hipMemsetAsync(c.out->float_count, 0, 2 * kSumBuckets * 8, c.st));
+  PDP_HIP_CHECK(hipMemsetAsync(c.out->float_sum, 0, 2 * kSumBuckets * 8, c.st));
+  PDP_HIP_CHECK(hipMemsetAsync(c.out->float_lowers, 0, 2 * kNLowers * 8, c.st));
+  return PDP_OK;
+}
+
+// the float stage of both paths: the lowers from minmax, `bins` (the path's
+// float kernels, given their grid: at most one 1,024-thread workgroup per CU,
+// whose bins fill its LDS, over `elems` elements), then k_h_final
+template <typename Bins>
+int float_stage(const Call& c, const unsigned long long* minmax, int64_t elems, int small_mask, Bins&& bins) {
+  if (int rc = launch("k_h_lowers", k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, c.st,
+                      minmax, c.out->float_lowers, c.out->float_n_lowers); rc != PDP_OK) return rc;
+  int dev = 0, cus = 256;
+  PDP_HIP_CHECK(hipGetDevice(&dev));
+  PDP_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int64_t gf = (elems + kFloatBlock - 1) / kFloatBlock;
+  gf = gf < 1 ? 1 : (gf < cus ? gf : cus);
+  if (int rc = bins((unsigned)gf); rc != PDP_OK) return rc;
+  return launch("k_h_final", k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, c.st, c.H, c.F,
+                c.out->float_max, small_mask);
+}
+
+struct HCall : Call {
+  HWs w;
+  HT t;
 };
 
 int hist_check(int32_t value_kind, int64_t n_rows, int64_t n_privacy_ids, int64_t n_partitions,
                const pdp_histogram_bins* out, void* workspace, uint64_t workspace_bytes, void* stream, HCall* c) {
-  if (out == nullptr || out->int_count == nullptr || out->int_sum == nullptr || out->int_max == nullptr ||
-      out->float_count == nullptr || out->float_sum == nullptr || out->float_max == nullptr ||
-      out->float_lowers == nullptr || out->float_n_lowers == nullptr)
-    return set_error(PDP_E_INVALID, "every pdp_histogram_bins output must be set");
-  if (n_rows < 0 || n_privacy_ids < 0 || n_partitions < 0) return set_error(PDP_E_INVALID, "sizes must be >= 0");
-  if (n_rows >= (int64_t)1 << 31) return set_error(PDP_E_UNSUPPORTED, "n_rows must be < 2^31 per shard");
+  if (int rc = call_check(out, {n_rows, n_privacy_ids, n_partitions}, n_rows, c); rc != PDP_OK) return rc;
   value_kind &= ~(PDP_HIST_FORCE_PAIR_TABLE | PDP_HIST_FORCE_PAIR_HASH);
   if (value_kind != PDP_VALUE_NONE && value_kind != PDP_VALUE_F64 && value_kind != PDP_VALUE_I64)
     return set_error(PDP_E_INVALID, "bad value_kind");
   if (bits_for(n_privacy_ids) + bits_for(n_partitions) > 63)
     return set_error(PDP_E_UNSUPPORTED, "pair key (privacy id bits + partition bits) exceeds 63 bits");
   c->w = hlayout(n_rows, n_privacy_ids, n_partitions);
-  if (workspace == nullptr || workspace_bytes < c->w.total)
-    return set_error(PDP_E_INVALID, "workspace smaller than pdp_dataset_histograms_workspace_bytes");
-  c->ws = (char*)workspace;
-  c->st = (hipStream_t)stream;
+  if (int rc = call_workspace(workspace, workspace_bytes, c->w.total, c->w.fmax,
+                              "workspace smaller than pdp_dataset_histograms_workspace_bytes", stream, c);
+      rc != PDP_OK) return rc;
   HT& t = c->t;
   t.n = n_rows;
   t.U = n_privacy_ids;
@@ -1812,9 +1792,6 @@ int hist_check(int32_t value_kind, int64_t n_rows, int64_t n_privacy_ids, int64_
   t.nb = hb_buckets(n_rows);
   t.n_supers = (t.nb + kHbFan - 1) / kHbFan;
   t.n_tiles = (n_rows + kHbTileRows - 1) / kHbTileRows;
-  c->H = IntHists{(unsigned long long*)out->int_count, (unsigned long long*)out->int_sum,
-                  (unsigned long long*)out->int_max};
-  c->F = FloatHists{(unsigned long long*)out->float_count, out->float_sum, (unsigned long long*)(c->ws + c->w.fmax)};
   return PDP_OK;
 }
 
@@ -1846,22 +1823,12 @@ int hist_pairs_bucketed(const HCall& c, const int64_t* privacy_id, const int64_t
                       sbase); rc != PDP_OK) return rc;
   if (int rc = launch("k_hb_scan_supers", k_hb_scan_supers, dim3(1), dim3(kHbFan), 0, st, t,
                       sbase); rc != PDP_OK) return rc;
-  const size_t lds1 = hb_l1_lds(value_kind);
-  const void* l1 = value_kind == PDP_VALUE_F64 ? (const void*)k_hb_l1<PDP_VALUE_F64>
-                   : value_kind == PDP_VALUE_I64 ? (const void*)k_hb_l1<PDP_VALUE_I64>
-                                                 : (const void*)k_hb_l1<PDP_VALUE_NONE>;
-  PDP_HIP_CHECK(hipFuncSetAttribute(l1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-  {
-    const HT tt = t;
-    const unsigned* cts_c = cts;
-    const unsigned* sbase_c = sbase;
-    void* args[] = {(void*)&tt, (void*)&privacy_id, (void*)&partition, (void*)&value, (void*)&cts_c,
-                    (void*)&sbase_c, (void*)&key1, (void*)&val1};
-    PDP_PROF_BEGIN("k_hb_l1", st);
-    PDP_HIP_CHECK(hipLaunchKernel(l1, dim3((unsigned)t.n_tiles), dim3(kHbThreads), args, lds1, st));
-    PDP_PROF_END(st);
-    PDP_HIP_CHECK(hipGetLastError());
-  }
+  if (int rc = launch_big_lds("k_hb_l1",
+                              value_kind == PDP_VALUE_F64   ? k_hb_l1<PDP_VALUE_F64>
+                              : value_kind == PDP_VALUE_I64 ? k_hb_l1<PDP_VALUE_I64>
+                                                            : k_hb_l1<PDP_VALUE_NONE>,
+                              dim3((unsigned)t.n_tiles), dim3(kHbThreads), hb_l1_lds(value_kind), st, t, privacy_id,
+                              partition, value, cts, sbase, key1, val1); rc != PDP_OK) return rc;
   PDP_HIP_CHECK(hipMemsetAsync(bcnt, 0, (uint64_t)(t.nb + 1) * 4, st));
   PDP_HIP_CHECK(hipMemsetAsync(bcur, 0, (uint64_t)t.nb * 4, st));
   const unsigned g2 = (unsigned)(t.n_supers * kHbK);
@@ -1883,24 +1850,11 @@ int hist_pairs_bucketed(const HCall& c, const int64_t* privacy_id, const int64_t
   if (pid_buckets) {
     PRec* prec = (PRec*)key1;  // level-1 records are dead after level 2 (16 bytes per row)
     unsigned* pruns = t.hb_R ? (unsigned*)(ws + w.hb_pruns) : nullptr;
-    const size_t lds = hb_pid_lds();
-    const void* f = hv ? (t.hb_R ? (const void*)k_hb_pid_pairs<true, true> : (const void*)k_hb_pid_pairs<true, false>)
-                       : (t.hb_R ? (const void*)k_hb_pid_pairs<false, true> : (const void*)k_hb_pid_pairs<false, false>);
-    PDP_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    {
-      const HT tt = t;
-      const unsigned* bst = bcnt;
-      const unsigned long long* k2 = key2;
-      const double* v2 = val2;
-      IntHists HH = c.H;
-      void* args[] = {(void*)&tt,     (void*)&bst,    (void*)&k2,      (void*)&v2,    (void*)&pidstat,
-                      (void*)&pkstat, (void*)&psum,   (void*)&HH,      (void*)&minmax, (void*)&pairsum,
-                      (void*)&prec,   (void*)&pruns,  (void*)&ctl};
-      PDP_PROF_BEGIN("k_hb_pid_pairs", st);
-      PDP_HIP_CHECK(hipLaunchKernel(f, dim3((unsigned)t.nb), dim3(kHbPidThreads), args, lds, st));
-      PDP_PROF_END(st);
-      PDP_HIP_CHECK(hipGetLastError());
-    }
+    if (int rc = launch_big_lds("k_hb_pid_pairs",
+                                hv ? (t.hb_R ? k_hb_pid_pairs<true, true> : k_hb_pid_pairs<true, false>)
+                                   : (t.hb_R ? k_hb_pid_pairs<false, true> : k_hb_pid_pairs<false, false>),
+                                dim3((unsigned)t.nb), dim3(kHbPidThreads), hb_pid_lds(), st, t, bcnt, key2, val2,
+                                pidstat, pkstat, psum, c.H, minmax, pairsum, prec, pruns, ctl); rc != PDP_OK) return rc;
     if (t.hb_R) {
       // ~1,024 workgroups: R ranges x G slices of the buckets
       int64_t G = 1024 / t.hb_R;
@@ -1919,10 +1873,22 @@ int hist_pairs_bucketed(const HCall& c, const int64_t* privacy_id, const int64_t
                 psum, c.H, minmax, pairsum, ctl);
 }
 
+// what every attempt of the pairs phase starts from: control words, pair-sum
+// range, the integer bins (the first attempt: the float bins too) and the
+// per-pid and per-partition statistics
+int hist_reset_pairs(const HCall& c, bool first) {
+  PDP_HIP_CHECK(hipMemsetAsync(c.ws + c.w.hb_ctl, 0, 16, c.st));
+  if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, c.st,
+                      (unsigned long long*)(c.ws + c.w.minmax)); rc != PDP_OK) return rc;
+  if (int rc = zero_outputs(c, first); rc != PDP_OK) return rc;
+  PDP_HIP_CHECK(hipMemsetAsync(c.ws + c.w.pidstat, 0, c.w.minmax - c.w.pidstat, c.st));  // pidstat .. psum
+  return PDP_OK;
+}
+
 // zero everything; k_h_rows + k_h_pairs (pair table, per-pid / per-partition
 // statistics, Linf histogram, pair-sum min / max)
 int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partition, const void* value,
-               int32_t value_kind, const pdp_histogram_bins* out) {
+               int32_t value_kind) {
   const HWs& w = c.w;
   const HT& t = c.t;
   char* ws = c.ws;
@@ -1932,20 +1898,10 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
   value_kind &= ~(PDP_HIST_FORCE_PAIR_TABLE | PDP_HIST_FORCE_PAIR_HASH);
   const bool bucketed = !force_table && hb_eligible(t.n);
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.err, 0, 16, st));
-  // the pair table (slots .. region scan) only for its own path; the per-pid
-  // and per-partition statistics for both
+  // the pair table (slots .. region scan) only for its own path
   if (!bucketed) PDP_HIP_CHECK(hipMemsetAsync(ws + w.slots, 0, w.pidstat - w.slots, st));
-  PDP_HIP_CHECK(hipMemsetAsync(ws + w.pidstat, 0, w.minmax - w.pidstat, st));  // pidstat .. psum
-  if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, st,
-                      (unsigned long long*)(ws + w.minmax)); rc != PDP_OK) return rc;
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.fmax, 0, 2 * kSumBuckets * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->int_count, 0, 5 * kLogBins * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->int_sum, 0, 5 * kLogBins * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->int_max, 0, 5 * kLogBins * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->float_count, 0, 2 * kSumBuckets * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->float_sum, 0, 2 * kSumBuckets * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->float_lowers, 0, 2 * kNLowers * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(ws + w.hb_ctl, 0, 16, st));
+  if (int rc = hist_reset_pairs(c, true); rc != PDP_OK) return rc;
   if (t.n == 0) return PDP_OK;
   if (privacy_id == nullptr || partition == nullptr || (value_kind != PDP_VALUE_NONE && value == nullptr))
     return set_error(PDP_E_INVALID, "NULL column");
@@ -1962,13 +1918,7 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
       PDP_HIP_CHECK(hipMemcpyAsync(&over, ws + w.hb_ctl + 8, 4, hipMemcpyDeviceToHost, st));
       PDP_HIP_CHECK(hipStreamSynchronize(st));
       if (!over) return PDP_OK;
-      PDP_HIP_CHECK(hipMemsetAsync(ws + w.hb_ctl, 0, 16, st));
-      if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, st,
-                          (unsigned long long*)(ws + w.minmax)); rc != PDP_OK) return rc;
-      PDP_HIP_CHECK(hipMemsetAsync(out->int_count, 0, 5 * kLogBins * 8, st));
-      PDP_HIP_CHECK(hipMemsetAsync(out->int_sum, 0, 5 * kLogBins * 8, st));
-      PDP_HIP_CHECK(hipMemsetAsync(out->int_max, 0, 5 * kLogBins * 8, st));
-      PDP_HIP_CHECK(hipMemsetAsync(ws + w.pidstat, 0, w.minmax - w.pidstat, st));  // pidstat .. psum
+      if (int rc = hist_reset_pairs(c, false); rc != PDP_OK) return rc;
     }
     PDP_HIP_CHECK(hipMemsetAsync(ws + w.slots, 0, w.pidstat - w.slots, st));  // the pair table
   }
@@ -1986,19 +1936,12 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
     const int rc = scan_u32(rbase, t.R, (unsigned*)(ws + w.rchunks), st);
     if (rc != PDP_OK) return rc;
   }
-  switch (value_kind) {
-    case PDP_VALUE_F64:
-      if (int rc = launch("k_h_rows", k_h_rows<PDP_VALUE_F64>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
-                          value, rbase, slots, err); rc != PDP_OK) return rc;
-      break;
-    case PDP_VALUE_I64:
-      if (int rc = launch("k_h_rows", k_h_rows<PDP_VALUE_I64>, dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition,
-                          value, rbase, slots, err); rc != PDP_OK) return rc;
-      break;
-    default:
-      if (int rc = launch("k_h_rows", k_h_rows<PDP_VALUE_NONE>, dim3(g), dim3(kBlock), 0, st, t, privacy_id,
-                          partition, value, rbase, slots, err); rc != PDP_OK) return rc;
-  }
+  if (int rc = launch("k_h_rows",
+                      value_kind == PDP_VALUE_F64   ? k_h_rows<PDP_VALUE_F64>
+                      : value_kind == PDP_VALUE_I64 ? k_h_rows<PDP_VALUE_I64>
+                                                    : k_h_rows<PDP_VALUE_NONE>,
+                      dim3(g), dim3(kBlock), 0, st, t, privacy_id, partition, value, rbase, slots,
+                      err); rc != PDP_OK) return rc;
   const int64_t n_chunks = ((int64_t)t.cap + kPairsChunk - 1) / kPairsChunk;  // upper bound of the used slots
   return launch("k_h_pairs", k_h_pairs, dim3((unsigned)n_chunks), dim3(kPairsBlock), 0, st, t, slots, rbase,
                 (unsigned long long*)(ws + w.pidstat), (unsigned long long*)(ws + w.pkstat), (double*)(ws + w.psum),
@@ -2006,11 +1949,12 @@ int hist_pairs(const HCall& c, const int64_t* privacy_id, const int64_t* partiti
 }
 
 // k_h_ids (partition part only when t.do_parts), lowers, float bins, final
-int hist_finish(const HCall& c, const pdp_histogram_bins* out) {
+int hist_finish(const HCall& c) {
   const HWs& w = c.w;
   const HT& t = c.t;
   char* ws = c.ws;
   hipStream_t st = c.st;
+  const pdp_histogram_bins* out = c.out;
   unsigned long long* minmax = (unsigned long long*)(ws + w.minmax);
   const unsigned long long* pkstat = (const unsigned long long*)(ws + w.pkstat);
   const double* psum = (const double*)(ws + w.psum);
@@ -2022,34 +1966,32 @@ int hist_finish(const HCall& c, const pdp_histogram_bins* out) {
                         dim3((unsigned)((m + kIdsThreads - 1) / kIdsThreads < 256 ? (m + kIdsThreads - 1) / kIdsThreads : 256)),
                         dim3(kIdsThreads), 0, st, t, (const unsigned long long*)(ws + w.pidstat), pkstat, psum, c.H,
                         minmax); rc != PDP_OK) return rc;
-  if (int rc = launch("k_h_lowers", k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, st,
-                      minmax, out->float_lowers, out->float_n_lowers); rc != PDP_OK) return rc;
-  // one 1024-thread workgroup per CU (120 KB of LDS each)
-  int dev = 0, cus = 256;
-  PDP_HIP_CHECK(hipGetDevice(&dev));
-  PDP_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   const int64_t mf = (int64_t)t.cap > t.P ? (int64_t)t.cap : t.P;
-  int64_t gf = (mf + kFloatBlock - 1) / kFloatBlock;
-  gf = gf < cus ? gf : cus;
-  const Slot* fslots = (const Slot*)(ws + w.slots);
-  const double* fpairsum = (const double*)(w.hb_pairsum ? ws + w.hb_pairsum : nullptr);
-  const unsigned* fctl = (const unsigned*)(ws + w.hb_ctl);
-  const unsigned* fbstart = (const unsigned*)(w.hb_bcnt ? ws + w.hb_bcnt : nullptr);
-  const PRec* fprec = (const PRec*)(ws + w.slots);
-  if (int rc = launch("k_h_float", k_h_float<false>, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, fslots,
-                      fpairsum, fctl, fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers,
-                      c.F); rc != PDP_OK) return rc;
-  if (int rc = launch("k_h_float_max", k_h_float<true>, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, fslots,
-                      fpairsum, fctl, fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers,
-                      c.F); rc != PDP_OK) return rc;
-  return launch("k_h_final", k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.H, c.F,
-                out->float_max, 0x1F);
+  return float_stage(c, minmax, mf, 0x1F, [&](unsigned gf) {
+    const Slot* fslots = (const Slot*)(ws + w.slots);
+    const double* fpairsum = (const double*)(w.hb_pairsum ? ws + w.hb_pairsum : nullptr);
+    const unsigned* fctl = (const unsigned*)(ws + w.hb_ctl);
+    const unsigned* fbstart = (const unsigned*)(w.hb_bcnt ? ws + w.hb_bcnt : nullptr);
+    const PRec* fprec = (const PRec*)(ws + w.slots);
+    if (int rc = launch("k_h_float", k_h_float<false>, dim3(gf), dim3(kFloatBlock), 0, st, t, fslots, fpairsum, fctl,
+                        fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers,
+                        c.F); rc != PDP_OK) return rc;
+    return launch("k_h_float_max", k_h_float<true>, dim3(gf), dim3(kFloatBlock), 0, st, t, fslots, fpairsum, fctl,
+                  fbstart, fprec, pkstat, psum, out->float_lowers, out->float_n_lowers, c.F);
+  });
 }
 
 }  // namespace
 }  // namespace pdp
 
 extern "C" {
+
+int pdp_dataset_histograms_workspace_bytes(int64_t n_rows, int64_t n_privacy_ids, int64_t n_partitions,
+                                           uint64_t* bytes) {
+  if (int rc = pdp::sizes_check({bytes}, {n_rows, n_privacy_ids, n_partitions}); rc != PDP_OK) return rc;
+  *bytes = pdp::hlayout(n_rows, n_privacy_ids, n_partitions).total;
+  return PDP_OK;
+}
 
 int pdp_dataset_histograms(const int64_t* privacy_id, const int64_t* partition, const void* value,
                            int32_t value_kind, int64_t n_rows, int64_t n_privacy_ids, int64_t n_partitions,
@@ -2058,8 +2000,8 @@ int pdp_dataset_histograms(const int64_t* privacy_id, const int64_t* partition, 
   pdp::HCall c;
   int rc = pdp::hist_check(value_kind, n_rows, n_privacy_ids, n_partitions, out, workspace, workspace_bytes, stream,
                            &c);
-  if (rc == PDP_OK) rc = pdp::hist_pairs(c, privacy_id, partition, value, value_kind, out);
-  if (rc == PDP_OK) rc = pdp::hist_finish(c, out);
+  if (rc == PDP_OK) rc = pdp::hist_pairs(c, privacy_id, partition, value, value_kind);
+  if (rc == PDP_OK) rc = pdp::hist_finish(c);
   return rc;
 }
 
@@ -2070,14 +2012,12 @@ int pdp_dataset_histograms_pairs(const int64_t* privacy_id, const int64_t* parti
   pdp::HCall c;
   int rc = pdp::hist_check(value_kind, n_rows, n_privacy_ids, n_partitions, out, workspace, workspace_bytes, stream,
                            &c);
-  return rc == PDP_OK ? pdp::hist_pairs(c, privacy_id, partition, value, value_kind, out) : rc;
+  return rc == PDP_OK ? pdp::hist_pairs(c, privacy_id, partition, value, value_kind) : rc;
 }
 
 int pdp_dataset_histograms_exchange_offsets(int64_t n_rows, int64_t n_privacy_ids, int64_t n_partitions,
                                             uint64_t* pkstat, uint64_t* psum, uint64_t* minmax) {
-  if (pkstat == nullptr || psum == nullptr || minmax == nullptr) return pdp::set_error(PDP_E_INVALID, "NULL argument");
-  if (n_rows < 0 || n_privacy_ids < 0 || n_partitions < 0)
-    return pdp::set_error(PDP_E_INVALID, "sizes must be >= 0");
+  if (int rc = pdp::sizes_check({pkstat, psum, minmax}, {n_rows, n_privacy_ids, n_partitions}); rc != PDP_OK) return rc;
   const pdp::HWs w = pdp::hlayout(n_rows, n_privacy_ids, n_partitions);
   *pkstat = w.pkstat;
   *psum = w.psum;
@@ -2093,7 +2033,7 @@ int pdp_dataset_histograms_finish(int32_t value_kind, int64_t n_rows, int64_t n_
                            &c);
   if (rc != PDP_OK) return rc;
   c.t.do_parts = partition_histograms != 0;
-  return pdp::hist_finish(c, out);
+  return pdp::hist_finish(c);
 }
 
 }  // extern "C"
@@ -2101,40 +2041,24 @@ int pdp_dataset_histograms_finish(int32_t value_kind, int64_t n_rows, int64_t n_
 namespace pdp {
 namespace {
 
-struct PCall {
+struct PCall : Call {
   PWs w;
   PT t;
-  char* ws;
-  hipStream_t st;
-  IntHists H;
-  FloatHists F;
 };
 
 int pre_check(int64_t n_rows, int64_t n_partitions, const pdp_histogram_bins* out, void* workspace,
               uint64_t workspace_bytes, void* stream, PCall* c) {
-  if (out == nullptr || out->int_count == nullptr || out->int_sum == nullptr || out->int_max == nullptr ||
-      out->float_count == nullptr || out->float_sum == nullptr || out->float_max == nullptr ||
-      out->float_lowers == nullptr || out->float_n_lowers == nullptr)
-    return set_error(PDP_E_INVALID, "every pdp_histogram_bins output must be set");
-  if (n_rows < 0 || n_partitions < 0) return set_error(PDP_E_INVALID, "sizes must be >= 0");
-  if (n_rows >= (int64_t)1 << 31) return set_error(PDP_E_UNSUPPORTED, "n_rows must be < 2^31 per shard");
+  if (int rc = call_check(out, {n_rows, n_partitions}, n_rows, c); rc != PDP_OK) return rc;
   c->w = playout(n_rows, n_partitions);
-  if (workspace == nullptr || workspace_bytes < c->w.total)
-    return set_error(PDP_E_INVALID, "workspace smaller than pdp_dataset_histograms_preaggregated_workspace_bytes");
-  c->ws = (char*)workspace;
-  c->st = (hipStream_t)stream;
   c->t = PT{n_rows, n_partitions, wtab_capacity(n_rows), 1};
-  c->H = IntHists{(unsigned long long*)out->int_count, (unsigned long long*)out->int_sum,
-                  (unsigned long long*)out->int_max};
-  c->F = FloatHists{(unsigned long long*)out->float_count, out->float_sum, (unsigned long long*)(c->ws + c->w.fmax)};
-  return PDP_OK;
+  return call_workspace(workspace, workspace_bytes, c->w.total, c->w.fmax,
+                        "workspace smaller than pdp_dataset_histograms_preaggregated_workspace_bytes", stream, c);
 }
 
 // zero everything; k_hp_rows (Linf histogram, per-partition statistics,
 // row-sum min / max, L0 / L1 weight sums)
 int pre_rows(const PCall& c, const int64_t* partition, const int64_t* count, const double* sum,
-             const int64_t* n_partitions_of_pid, const int64_t* n_contributions_of_pid,
-             const pdp_histogram_bins* out) {
+             const int64_t* n_partitions_of_pid, const int64_t* n_contributions_of_pid) {
   const PWs& w = c.w;
   const PT& t = c.t;
   char* ws = c.ws;
@@ -2144,12 +2068,7 @@ int pre_rows(const PCall& c, const int64_t* partition, const int64_t* count, con
   if (int rc = launch("k_h_init", k_h_init, dim3(1), dim3(64), 0, st,
                       (unsigned long long*)(ws + w.minmax)); rc != PDP_OK) return rc;
   PDP_HIP_CHECK(hipMemsetAsync(ws + w.fmax, 0, w.total - w.fmax, st));  // fmax, weight sums, weight table
-  PDP_HIP_CHECK(hipMemsetAsync(out->int_count, 0, 5 * kLogBins * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->int_sum, 0, 5 * kLogBins * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->int_max, 0, 5 * kLogBins * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->float_count, 0, 2 * kSumBuckets * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->float_sum, 0, 2 * kSumBuckets * 8, st));
-  PDP_HIP_CHECK(hipMemsetAsync(out->float_lowers, 0, 2 * kNLowers * 8, st));
+  if (int rc = zero_outputs(c, true); rc != PDP_OK) return rc;
   if (t.n == 0) return PDP_OK;
   if (partition == nullptr || count == nullptr || sum == nullptr || n_partitions_of_pid == nullptr ||
       n_contributions_of_pid == nullptr)
@@ -2162,7 +2081,7 @@ int pre_rows(const PCall& c, const int64_t* partition, const int64_t* count, con
 }
 
 // weighted L0 / L1 bins, partition histograms (t.do_parts), lowers, float bins
-int pre_finish(const PCall& c, const double* sum, const pdp_histogram_bins* out) {
+int pre_finish(const PCall& c, const double* sum) {
   const PWs& w = c.w;
   const PT& t = c.t;
   char* ws = c.ws;
@@ -2178,19 +2097,12 @@ int pre_finish(const PCall& c, const double* sum, const pdp_histogram_bins* out)
     if (int rc = launch("k_hp_ids", k_hp_ids, dim3(grid_for(t.P, 2048)), dim3(kBlock), 0, st, t, pkrows,
                         (const unsigned long long*)(ws + w.pkcount), psum, c.H, minmax); rc != PDP_OK) return rc;
   }
-  if (int rc = launch("k_h_lowers", k_h_lowers, dim3((kNLowers + kBlock - 1) / kBlock, 2), dim3(kBlock), 0, st,
-                      minmax, out->float_lowers, out->float_n_lowers); rc != PDP_OK) return rc;
-  int dev = 0, cus = 256;
-  PDP_HIP_CHECK(hipGetDevice(&dev));
-  PDP_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int64_t mf = t.n > t.P ? t.n : t.P;
-  int64_t gf = (mf + kFloatBlock - 1) / kFloatBlock;
-  gf = gf < 1 ? 1 : (gf < cus ? gf : cus);
-  if (t.n > 0 && sum == nullptr) return set_error(PDP_E_INVALID, "NULL column");
-  if (int rc = launch("k_hp_float", k_hp_float, dim3((unsigned)gf), dim3(kFloatBlock), 0, st, t, sum, pkrows, psum,
-                      out->float_lowers, out->float_n_lowers, c.F); rc != PDP_OK) return rc;
-  return launch("k_h_final", k_h_final, dim3((2 * kSumBuckets + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c.H, c.F,
-                out->float_max, (1 << H_LINF) | (1 << H_COUNT) | (1 << H_PIDS));
+  return float_stage(c, minmax, t.n > t.P ? t.n : t.P, (1 << H_LINF) | (1 << H_COUNT) | (1 << H_PIDS),
+                     [&](unsigned gf) {
+    if (t.n > 0 && sum == nullptr) return set_error(PDP_E_INVALID, "NULL column");
+    return launch("k_hp_float", k_hp_float, dim3(gf), dim3(kFloatBlock), 0, st, t, sum, pkrows, psum,
+                  c.out->float_lowers, c.out->float_n_lowers, c.F);
+  });
 }
 
 }  // namespace
@@ -2199,8 +2111,7 @@ int pre_finish(const PCall& c, const double* sum, const pdp_histogram_bins* out)
 extern "C" {
 
 int pdp_dataset_histograms_preaggregated_workspace_bytes(int64_t n_rows, int64_t n_partitions, uint64_t* bytes) {
-  if (bytes == nullptr) return pdp::set_error(PDP_E_INVALID, "NULL argument");
-  if (n_rows < 0 || n_partitions < 0) return pdp::set_error(PDP_E_INVALID, "sizes must be >= 0");
+  if (int rc = pdp::sizes_check({bytes}, {n_rows, n_partitions}); rc != PDP_OK) return rc;
   *bytes = pdp::playout(n_rows, n_partitions).total;
   return PDP_OK;
 }
@@ -2212,15 +2123,12 @@ int pdp_dataset_histograms_preaggregated_rows(const int64_t* partition, const in
                                               uint64_t workspace_bytes, void* stream) {
   pdp::PCall c;
   const int rc = pdp::pre_check(n_rows, n_partitions, out, workspace, workspace_bytes, stream, &c);
-  return rc == PDP_OK ? pdp::pre_rows(c, partition, count, sum, n_partitions_of_pid, n_contributions_of_pid, out)
-                      : rc;
+  return rc == PDP_OK ? pdp::pre_rows(c, partition, count, sum, n_partitions_of_pid, n_contributions_of_pid) : rc;
 }
 
 int pdp_dataset_histograms_preaggregated_exchange_offsets(int64_t n_rows, int64_t n_partitions, uint64_t* pk_rows,
                                                           uint64_t* pk_count, uint64_t* psum, uint64_t* minmax) {
-  if (pk_rows == nullptr || pk_count == nullptr || psum == nullptr || minmax == nullptr)
-    return pdp::set_error(PDP_E_INVALID, "NULL argument");
-  if (n_rows < 0 || n_partitions < 0) return pdp::set_error(PDP_E_INVALID, "sizes must be >= 0");
+  if (int rc = pdp::sizes_check({pk_rows, pk_count, psum, minmax}, {n_rows, n_partitions}); rc != PDP_OK) return rc;
   const pdp::PWs w = pdp::playout(n_rows, n_partitions);
   *pk_rows = w.pkrows;
   *pk_count = w.pkcount;
@@ -2231,9 +2139,7 @@ int pdp_dataset_histograms_preaggregated_exchange_offsets(int64_t n_rows, int64_
 
 int pdp_dataset_histograms_preaggregated_weight_offsets(int64_t n_rows, int64_t n_partitions, uint64_t* wsmall,
                                                         uint64_t* wtab, uint64_t* wtab_slots) {
-  if (wsmall == nullptr || wtab == nullptr || wtab_slots == nullptr)
-    return pdp::set_error(PDP_E_INVALID, "NULL argument");
-  if (n_rows < 0 || n_partitions < 0) return pdp::set_error(PDP_E_INVALID, "sizes must be >= 0");
+  if (int rc = pdp::sizes_check({wsmall, wtab, wtab_slots}, {n_rows, n_partitions}); rc != PDP_OK) return rc;
   const pdp::PWs w = pdp::playout(n_rows, n_partitions);
   *wsmall = w.wsmall;
   *wtab = w.wtab;
@@ -2243,16 +2149,13 @@ int pdp_dataset_histograms_preaggregated_weight_offsets(int64_t n_rows, int64_t 
 
 int pdp_dataset_histograms_weight_bins(const uint64_t* keys, const double* weights, int64_t n,
                                        const pdp_histogram_bins* out, void* stream) {
-  if (out == nullptr || out->int_count == nullptr || out->int_sum == nullptr || out->int_max == nullptr)
-    return pdp::set_error(PDP_E_INVALID, "the integer pdp_histogram_bins outputs must be set");
+  pdp::Call c;
+  if (int rc = pdp::bins_check(out, true, &c); rc != PDP_OK) return rc;
   if (n < 0) return pdp::set_error(PDP_E_INVALID, "n must be >= 0");
   if (n == 0) return PDP_OK;
   if (keys == nullptr || weights == nullptr) return pdp::set_error(PDP_E_INVALID, "NULL list");
-  hipStream_t st = (hipStream_t)stream;
-  const pdp::IntHists H{(unsigned long long*)out->int_count, (unsigned long long*)out->int_sum,
-                        (unsigned long long*)out->int_max};
   return pdp::launch("k_hp_weight_list", pdp::k_hp_weight_list, dim3(pdp::grid_for(n, (int64_t)1 << 30)),
-                dim3(pdp::kBlock), 0, st, (const unsigned long long*)keys, weights, n, H);
+                     dim3(pdp::kBlock), 0, (hipStream_t)stream, (const unsigned long long*)keys, weights, n, c.H);
 }
 
 int pdp_dataset_histograms_preaggregated_finish(const double* sum, int64_t n_rows, int64_t n_partitions,
@@ -2263,7 +2166,7 @@ int pdp_dataset_histograms_preaggregated_finish(const double* sum, int64_t n_row
   const int rc = pdp::pre_check(n_rows, n_partitions, out, workspace, workspace_bytes, stream, &c);
   if (rc != PDP_OK) return rc;
   c.t.do_parts = partition_histograms != 0;
-  return pdp::pre_finish(c, sum, out);
+  return pdp::pre_finish(c, sum);
 }
 
 int pdp_dataset_histograms_preaggregated(const int64_t* partition, const int64_t* count, const double* sum,
@@ -2272,8 +2175,8 @@ int pdp_dataset_histograms_preaggregated(const int64_t* partition, const int64_t
                                          void* workspace, uint64_t workspace_bytes, void* stream) {
   pdp::PCall c;
   int rc = pdp::pre_check(n_rows, n_partitions, out, workspace, workspace_bytes, stream, &c);
-  if (rc == PDP_OK) rc = pdp::pre_rows(c, partition, count, sum, n_partitions_of_pid, n_contributions_of_pid, out);
-  if (rc == PDP_OK) rc = pdp::pre_finish(c, sum, out);
+  if (rc == PDP_OK) rc = pdp::pre_rows(c, partition, count, sum, n_partitions_of_pid, n_contributions_of_pid);
+  if (rc == PDP_OK) rc = pdp::pre_finish(c, sum);
   return rc;
 }
 

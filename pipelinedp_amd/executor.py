@@ -930,16 +930,9 @@ def dataset_histograms(pid, pk, value, *, n_privacy_ids: int, n_partitions: int,
         vk |= N.HIST_FORCE_PAIR_TABLE
     if force_pair_hash:   # tests: pair-keyed buckets instead of privacy-id buckets
         vk |= N.HIST_FORCE_PAIR_HASH
-    nbytes = ctypes.c_uint64()
-    N.check(lib.pdp_dataset_histograms_workspace_bytes(n, int(n_privacy_ids), int(n_partitions),
-                                                      ctypes.byref(nbytes)),
-            "pdp_dataset_histograms_workspace_bytes")
-    ws = (workspace or BoundWorkspace()).get(nbytes.value, device)
-    out = _histogram_outputs(device)
-    s = N.HistogramBins(**{k: _ptr(v) for k, v in out.items()})
-    from pipelinedp_amd import parallel
-    world, rank = parallel.world_info(group)
     args = (int(n_privacy_ids), int(n_partitions))
+    nbytes, = _u64_results(lib.pdp_dataset_histograms_workspace_bytes, 1, n, *args)
+    ws, out, s, parallel, world, rank = _histogram_setup(device, nbytes, workspace, group)
     if world == 1:
         N.check(lib.pdp_dataset_histograms(_ptr(pid), _ptr(pk), _ptr(value) if value is not None else None, vk, n,
                                            *args, ctypes.byref(s), _ptr(ws), int(ws.numel()), _stream(stream)),
@@ -954,14 +947,10 @@ def dataset_histograms(pid, pk, value, *, n_privacy_ids: int, n_partitions: int,
                                                  vk, n, *args, ctypes.byref(s), _ptr(ws), int(ws.numel()),
                                                  _stream(stream)),
                 "pdp_dataset_histograms_pairs")
-        offs = [ctypes.c_uint64() for _ in range(3)]
-        N.check(lib.pdp_dataset_histograms_exchange_offsets(n, *args, *[ctypes.byref(o) for o in offs]),
-                "pdp_dataset_histograms_exchange_offsets")
+        offs = _u64_results(lib.pdp_dataset_histograms_exchange_offsets, 3, n, *args)
         P = int(n_partitions)
-        pkstat = ws[offs[0].value:offs[0].value + 8 * P].view(torch.int64)
-        psum = ws[offs[1].value:offs[1].value + 8 * P].view(torch.float64)
-        minmax = ws[offs[2].value:offs[2].value + 16].view(torch.int64)
-        parallel.exchange_histogram_stats(pkstat, psum, minmax, group)
+        parallel.exchange_histogram_stats(_ws_view(ws, offs[0], P, torch.int64), _ws_view(ws, offs[1], P, torch.float64),
+                                          _ws_view(ws, offs[2], 2, torch.int64), group)
         N.check(lib.pdp_dataset_histograms_finish(vk, n, *args, 1 if rank == 0 else 0, ctypes.byref(s), _ptr(ws),
                                                   int(ws.numel()), _stream(stream)),
                 "pdp_dataset_histograms_finish")
@@ -1041,6 +1030,28 @@ def _histogram_outputs(device):
     }
 
 
+def _u64_results(fn, k, *args):
+    """the k uint64 results (sizes, workspace offsets) that `fn(*args, ...)` writes"""
+    res = [ctypes.c_uint64() for _ in range(k)]
+    N.check(fn(*args, *[ctypes.byref(r) for r in res]), fn.__name__)
+    return [r.value for r in res]
+
+
+def _ws_view(ws, offset, count, dtype):
+    """`count` 64-bit elements at byte `offset` of a workspace, as `dtype`"""
+    return ws[offset:offset + 8 * count].view(dtype)
+
+
+def _histogram_setup(device, nbytes, workspace, group):
+    """what the two histogram functions set up alike: (workspace tensor, output
+    bins, their HistogramBins struct, the parallel module, world, rank)"""
+    ws = (workspace or BoundWorkspace()).get(nbytes, device)
+    out = _histogram_outputs(device)
+    s = N.HistogramBins(**{k: _ptr(v) for k, v in out.items()})
+    from pipelinedp_amd import parallel
+    return (ws, out, s, parallel) + tuple(parallel.world_info(group))
+
+
 def dataset_histograms_preaggregated(pk, count, total, n_partitions_of_pid, n_contributions_of_pid, *,
                                      n_partitions: int, stream=None,
                                      workspace: Optional[BoundWorkspace] = None,
@@ -1063,16 +1074,10 @@ def dataset_histograms_preaggregated(pk, count, total, n_partitions_of_pid, n_co
     _check_col(total, "sum", (torch.float64,), n, device)
     _check_col(n_partitions_of_pid, "n_partitions", (torch.int64,), n, device)
     _check_col(n_contributions_of_pid, "n_contributions", (torch.int64,), n, device)
-    nbytes = ctypes.c_uint64()
-    N.check(lib.pdp_dataset_histograms_preaggregated_workspace_bytes(n, int(n_partitions), ctypes.byref(nbytes)),
-            "pdp_dataset_histograms_preaggregated_workspace_bytes")
-    ws = (workspace or BoundWorkspace()).get(nbytes.value, device)
-    out = _histogram_outputs(device)
-    s = N.HistogramBins(**{k: _ptr(v) for k, v in out.items()})
-    cols = (_ptr(pk), _ptr(count), _ptr(total), _ptr(n_partitions_of_pid), _ptr(n_contributions_of_pid))
-    from pipelinedp_amd import parallel
-    world, rank = parallel.world_info(group)
     P = int(n_partitions)
+    nbytes, = _u64_results(lib.pdp_dataset_histograms_preaggregated_workspace_bytes, 1, n, P)
+    ws, out, s, parallel, world, rank = _histogram_setup(device, nbytes, workspace, group)
+    cols = (_ptr(pk), _ptr(count), _ptr(total), _ptr(n_partitions_of_pid), _ptr(n_contributions_of_pid))
     if world == 1:
         N.check(lib.pdp_dataset_histograms_preaggregated(*cols, n, P, ctypes.byref(s), _ptr(ws), int(ws.numel()),
                                                          _stream(stream)),
@@ -1081,21 +1086,14 @@ def dataset_histograms_preaggregated(pk, count, total, n_partitions_of_pid, n_co
         N.check(lib.pdp_dataset_histograms_preaggregated_rows(*cols, n, P, ctypes.byref(s), _ptr(ws),
                                                               int(ws.numel()), _stream(stream)),
                 "pdp_dataset_histograms_preaggregated_rows")
-        offs = [ctypes.c_uint64() for _ in range(4)]
-        N.check(lib.pdp_dataset_histograms_preaggregated_exchange_offsets(n, P, *[ctypes.byref(o) for o in offs]),
-                "pdp_dataset_histograms_preaggregated_exchange_offsets")
-        pk_rows = ws[offs[0].value:offs[0].value + 8 * P].view(torch.int64)
-        pk_count = ws[offs[1].value:offs[1].value + 8 * P].view(torch.int64)
-        psum = ws[offs[2].value:offs[2].value + 8 * P].view(torch.float64)
-        minmax = ws[offs[3].value:offs[3].value + 16].view(torch.int64)
-        parallel.exchange_preaggregated_stats(pk_rows, pk_count, psum, minmax, group)
+        offs = _u64_results(lib.pdp_dataset_histograms_preaggregated_exchange_offsets, 4, n, P)
+        parallel.exchange_preaggregated_stats(_ws_view(ws, offs[0], P, torch.int64), _ws_view(ws, offs[1], P, torch.int64),
+                                              _ws_view(ws, offs[2], P, torch.float64),
+                                              _ws_view(ws, offs[3], 2, torch.int64), group)
         # L0 / L1 weight sums: global before rounding (one owner rank per value)
-        woff = [ctypes.c_uint64() for _ in range(3)]
-        N.check(lib.pdp_dataset_histograms_preaggregated_weight_offsets(n, P, *[ctypes.byref(o) for o in woff]),
-                "pdp_dataset_histograms_preaggregated_weight_offsets")
-        wsmall = ws[woff[0].value:woff[0].value + 8 * 2000].view(torch.float64)
-        slots = woff[2].value
-        wtab = ws[woff[1].value:woff[1].value + 16 * slots].view(torch.int64).view(slots, 2)
+        wsmall_off, wtab_off, slots = _u64_results(lib.pdp_dataset_histograms_preaggregated_weight_offsets, 3, n, P)
+        wsmall = _ws_view(ws, wsmall_off, N.HIST_WEIGHT_SMALL, torch.float64)
+        wtab = _ws_view(ws, wtab_off, 2 * slots, torch.int64).view(slots, 2)
         wkeys, wsums = parallel.exchange_preaggregated_weights(wsmall, wtab, group)
         N.check(lib.pdp_dataset_histograms_preaggregated_finish(_ptr(total), n, P, 1 if rank == 0 else 0,
                                                                 ctypes.byref(s), _ptr(ws), int(ws.numel()),

@@ -365,6 +365,7 @@ STRUCTURE_N = (1, 63, 64, 65,
                1572864, 1572865)        # 1,024 buckets (1,024 range workgroups, per = 1) / 1,025 (per = 2)
 STRUCTURE_P = (2048, 2049,              # one partition range / two
                4096, 4097,              # one pair-table region / two
+               131072, 131073,          # 64 ranges (one wave chunk of k_hb_pid_pairs' range scan) / 65
                262144, 262145)          # 128 ranges (kHbRangeMax) / 129: per-pair partition atomics
 STRUCTURE_P_ROWS = 20000
 
