@@ -35,10 +35,15 @@
 //    updated with device-scope atomics.
 //
 // Where the code lives: every kernel above is in this file but the k_scan_*
-// (pdp_scan.hip, scan_u32) and the range merge (pdp_bound_merge.hip); this
-// file also holds validate, the plan (make_plan, layout, make_kp) and the C
-// entry points.  pdp_bound_plan.h: the shared constants, Plan, Ws, KP,
-// PairRecords; pdp_bound_keys.h: device helpers of more than one file.
+// (pdp_scan.hip, scan_u32) and the range merge (pdp_bound_merge.hip); after
+// the kernels come their launch chains and the C entry points that launch.
+// What they run on is decided in pdp_bound_planner.hip, host code only:
+// validate, the plan (make_plan), layout, make_kp, check_ws, pdp_bound_plan
+// and pdp_bound_workspace_bytes; it asks this file for the LDS sizes of
+// StageLds / SieveShape (l1_stage_bytes, sieve_stage_bytes, sieve_slot_bits).
+// pdp_bound_plan.h: the shared constants, Plan, Ws, KP, PairRecords, the typed
+// view of a workspace region (at / at_opt) and the planner's declarations;
+// pdp_bound_keys.h: device helpers of more than one file.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -48,16 +53,6 @@
 
 namespace pdp {
 namespace {
-
-constexpr int64_t kL1LocalLds = 150 * 1024;  // tile-local level 1: LDS cap (one 1,024-thread workgroup per CU)
-size_t l1_stage_bytes(int key_format);       // LDS of one level-1 stage (after StageLds)
-// tile-local level 1 bucket counts in LDS: u32 per bucket when they fit,
-// else two u16 per word, flushed every half tile (32,768 rows: no carry) to
-// counts_tm (first half) and counts_tm2 (second half)
-inline int64_t l1_hist_bytes(int64_t n_buckets, bool u16) { return ((u16 ? 2 : 4) * n_buckets + 15) / 16 * 16; }
-inline bool l1_hist_u16(int key_format, int64_t n_buckets) {
-  return (int64_t)l1_stage_bytes(key_format) + l1_hist_bytes(n_buckets, false) > kL1LocalLds;
-}
 
 // ---- threshold sieve (Plan.sieve) ----------------------------------------
 // With cross-partition sampling, a privacy id keeps the l0 pairs of smallest
@@ -95,18 +90,6 @@ struct SieveShape {
                 "sieve flushes per tile");
   static_assert(kCap <= 65535, "u16 run offsets");
 };
-constexpr int kSieveThreads2 = 512;
-constexpr int64_t kSieveLds2 = 80 * 1024 - 256;  // two 512-thread workgroups per CU
-// a tile's flush blocks lie back to back from tile * kSieveTileStride, its
-// band list at tile * kBandTileStride
-// (strides padded by 4 KiB measured 6 % slower at C3, profiles/r05/ab/ab1_l1_placement.txt)
-// non-temporal loads (ld_nt) of the columns level 1 streams and of the band
-// lists k_band_scan streams (C3 0.277 -> 0.255 ms); measured neutral or worse
-// and not used: k_scatter_l1_local's key loads (C4 +0.03 ms), level 2's run
-// loads and the bucket kernel's record stream (profiles/r05/ab/ab5_nt_loads.txt)
-constexpr int64_t kSieveTileStride = kTileRows;
-constexpr int64_t kBandTileStride = kTileRows;
-constexpr int kSieveMaxT16 = 1 << 15;                          // t <= 1/2
 // k_sieve_rescan: a 16 KiB LDS Bloom filter (a 64 KiB one limits the CU to
 // two workgroups, and the rescan then streams at 3.7 instead of 6.1 TB/s:
 // tools/stream_bench.hip, profiles/r03/stream_bench.txt); above
@@ -115,479 +98,6 @@ constexpr int kBloomWords = 4096;  // == 1 << kBloomBits
 constexpr unsigned kBloomMaxIds = 8192;
 constexpr int kRescanThreads = 512;
 constexpr int kRescanBlocks = 1024;
-// tile groups per level-2 workgroup with the sieve, at most: the plan takes
-// as many as keep a workgroup's expected records (tiles x candidates per tile
-// / super-buckets) within one LDS window (kL2Target), since a second window
-// holding a few hundred records costs as much latency as a full one; and no
-// more than one level-1 slot per level-2 thread
-constexpr int kSieveL2Groups = 4;
-constexpr double kL2Target = 7000.0;
-size_t sieve_stage_bytes(int key_format, int threads);  // LDS of the sieve's level-1 stage (after StageLds)
-// the side band (Plan.band): rows with t <= pair hash < t2 = 2t leave level 1
-// as (privacy id << 32 | row) in a per-tile list, through a per-wave LDS queue
-// written out 64 entries at a time; the fix-up reads that list instead of the
-// whole privacy-id column, and only a privacy id with fewer than l0 distinct
-// pairs below t2 still needs the rescan
-constexpr int kBandQueue = 128;
-inline int64_t sieve_band_lds(int threads) { return (threads / 64) * kBandQueue * 8; }
-// LDS of a sieve workgroup: stage, bucket counts (u32, or u16 pairs), band queues
-inline int64_t sieve_lds(int key_format, int threads, int64_t n_buckets, bool u16, bool band) {
-  return ((int64_t)sieve_stage_bytes(key_format, threads) + 7) / 8 * 8 + l1_hist_bytes(n_buckets, u16) +
-         (band ? sieve_band_lds(threads) : 0);
-}
-
-
-int64_t per_pid_lds(const pdp_bound_config* c) {
-  const int64_t l0 = c->l0;
-  const int64_t pair = 4 + (c->linf > 0 ? 8 * (int64_t)c->linf : 24);
-  return l0 * 8 + l0 * pair;  // pair sketch + per-pair state
-}
-
-bool test_hooks_enabled();
-// The plan with at most 2^max_bucket_bits privacy ids per bucket (make_plan
-// lowers it until the bucket kernel's LDS fits).
-Plan make_plan_capped(const pdp_bound_config* c, int max_bucket_bits) {
-  Plan p{};
-  p.pk_bits = bits_for(c->n_partitions);
-  const int64_t per_pid = per_pid_lds(c);
-  // the bucket kernel's workgroup: 512 threads (on request) only where the
-  // per-partition-range scan fits one thread per range
-  const int64_t n_ranges_est = (c->n_partitions + kRangeParts - 1) >> kRangeBits;
-  p.bucket_threads = c->bucket_threads == kBucketThreads / 2 &&
-                             (n_ranges_est <= kBucketThreads / 2 || n_ranges_est > kMaxRanges)
-                         ? kBucketThreads / 2
-                         : kBucketThreads;
-  const int64_t max_pids = (p.bucket_threads == kBucketThreads ? kLdsBudget : kLdsBudget2) / per_pid;
-  int s = -1, s2 = 0;
-  if (max_pids >= 16) {
-    s = 0;
-    while (((int64_t)2 << s) <= max_pids) ++s;          // largest 2^s <= max_pids
-    if (test_hooks_enabled()) {  // test hook: smaller buckets (PIPELINEDP_AMD_BUCKET_BITS)
-      const char* e = std::getenv("PIPELINEDP_AMD_BUCKET_BITS");
-      if (e != nullptr && std::atoi(e) >= 4 && std::atoi(e) < s) s = std::atoi(e);
-    }
-    if (s > max_bucket_bits) s = max_bucket_bits;
-    const int u_bits = bits_for(c->n_privacy_ids);
-    if (s > u_bits) s = u_bits;                          // one bucket covers all pids
-    const int64_t nb = (c->n_privacy_ids + ((int64_t)1 << s) - 1) >> s;
-    if (nb > kSingleLevelMax) {
-      // two levels: level 2's input runs are a stage's rows of one
-      // super-bucket (kL1Rows / supers), its output runs a window's rows of
-      // one bucket (kL2Rows / 2^s2); take the s2 whose shorter run is longest
-      // (C3: 77 supers x 64 buckets, C2: 62 x 32)
-      int lo = 1;
-      while (((nb + ((int64_t)1 << lo) - 1) >> lo) > kMaxSupers) ++lo;
-      double best = -1.0;
-      for (int c = lo; c <= lo + 3 && ((int64_t)1 << c) < nb; ++c) {
-        const double supers = (double)((nb + ((int64_t)1 << c) - 1) >> c);
-        const double score = std::min((double)kL1Rows / supers, (double)kL2Rows / (double)((int64_t)1 << c));
-        if (score > best) {
-          best = score;
-          s2 = c;
-        }
-      }
-    }
-    // pair keys: random bits above rand_shift = pk_bits + bucket_bits
-    if (nb > kMaxBuckets || 64 - p.pk_bits - s < kMinRandomBits) s = -1;
-  }
-  const int auto_algo = s >= 0 ? PDP_ALGO_BUCKETED : PDP_ALGO_GLOBAL_SKETCH;
-  p.algorithm = c->algorithm == PDP_ALGO_AUTO ? auto_algo : c->algorithm;
-  if (p.algorithm == PDP_ALGO_BUCKETED && s < 0) p.algorithm = -1;  // infeasible
-  p.bucket_bits = s < 0 ? 0 : s;
-  p.super_bits = s < 0 ? 0 : s2;
-  p.rand_shift = p.pk_bits + p.bucket_bits;
-  p.n_buckets = (c->n_privacy_ids + ((int64_t)1 << p.bucket_bits) - 1) >> p.bucket_bits;
-  p.n_supers = (p.n_buckets + ((int64_t)1 << p.super_bits) - 1) >> p.super_bits;
-  p.n_tiles = (c->n_rows + kTileRows - 1) / kTileRows;
-  if (p.n_tiles < 1) p.n_tiles = 1;
-  p.lds_bytes = ((int64_t)1 << p.bucket_bits) * per_pid;
-  p.range_bits = kRangeBits;
-  p.n_fine = (c->n_partitions + kRangeParts - 1) >> kRangeBits;
-  p.two_level = p.n_fine > kMaxRanges;
-  if (p.two_level)
-    while (((c->n_partitions + ((int64_t)1 << p.range_bits) - 1) >> p.range_bits) > kCoarseRanges) ++p.range_bits;
-  p.n_ranges = (int)((c->n_partitions + ((int64_t)1 << p.range_bits) - 1) >> p.range_bits);
-  const bool ranges_ok = p.n_ranges <= kMaxRanges;
-  if (p.algorithm != PDP_ALGO_BUCKETED) {
-    p.merge = 0;
-  } else if (c->merge == PDP_MERGE_AUTO) {
-    p.merge = ranges_ok ? PDP_MERGE_RANGES : PDP_MERGE_ATOMIC;
-  } else {
-    p.merge = c->merge;
-    if (p.merge == PDP_MERGE_RANGES && !ranges_ok) p.algorithm = -1;  // infeasible
-  }
-  if (p.merge == PDP_MERGE_RANGES) {
-    // per-bucket range histogram + cursors + block-scan scratch after the sketches
-    p.lds_bytes += (2 * (int64_t)p.n_ranges + p.bucket_threads / 64 + 1) * 4;
-  }
-  // row records of the partition passes: u32 (sub-bucket, local pid,
-  // partition) with bit 31 = dead when those fields fit (COMPACT); else the
-  // level-1 u64 packed record with a tile-relative row, then COMPACT pairs
-  // (PACKED); else the u64 pair key + u32 row (WIDE)
-  const bool compact_ok = p.super_bits + p.bucket_bits + p.pk_bits <= 31;
-  const bool packed_ok = p.bucket_bits + p.pk_bits <= 31 &&
-                         p.super_bits + p.bucket_bits + p.pk_bits <= 64 - 1 - kTileRowBits;
-  // PACKED level 1 with WIDE records from level 2 on (tile-local level 1 only)
-  const bool packed_wide_ok = p.super_bits + p.bucket_bits + p.pk_bits <= 64 - 1 - kTileRowBits;
-  // ... or with one u64 per record (PACKED64): the row above the bucket-local
-  // pid and partition, all ones reserved for dead records
-  const int row_bits = 64 - p.bucket_bits - p.pk_bits;
-  const bool packed64_ok = packed_wide_ok && (row_bits >= 33 || c->n_rows < ((int64_t)1 << row_bits) - 2);
-  p.key_format = 0;
-  p.n_stages = (c->n_rows + kL1Rows - 1) / kL1Rows;
-  p.l1_local = 0;
-  if (p.algorithm == PDP_ALGO_BUCKETED) {
-    // tile-local level 1: two levels, and the bucket counts in its LDS
-    auto local_fits = [&](int fmt) {
-      return p.super_bits > 0 &&
-             (int64_t)l1_stage_bytes(fmt) + l1_hist_bytes(p.n_buckets, true) <= kL1LocalLds;
-    };
-    const int want = c->key_format;
-    if (want == PDP_KEYS_AUTO) {
-      // tile-local: PACKED (one u64 array at level 1, so level 2 reads each
-      // run as one span), else PACKED_WIDE; else COMPACT / PACKED / WIDE
-      if (packed_ok && local_fits(PDP_KEYS_PACKED))
-        p.key_format = PDP_KEYS_PACKED;
-      else if (!packed_ok && packed64_ok && local_fits(PDP_KEYS_PACKED64))
-        p.key_format = PDP_KEYS_PACKED64;
-      else if (!packed_ok && packed_wide_ok && local_fits(PDP_KEYS_PACKED_WIDE))
-        p.key_format = PDP_KEYS_PACKED_WIDE;
-      else
-        p.key_format = compact_ok ? PDP_KEYS_COMPACT : (packed_ok ? PDP_KEYS_PACKED : PDP_KEYS_WIDE);
-    } else if ((want == PDP_KEYS_COMPACT && !compact_ok) || (want == PDP_KEYS_PACKED && !packed_ok) ||
-               (want == PDP_KEYS_PACKED_WIDE && !(packed_wide_ok && local_fits(PDP_KEYS_PACKED_WIDE))) ||
-               (want == PDP_KEYS_PACKED64 && !(packed64_ok && local_fits(PDP_KEYS_PACKED64)))) {
-      p.algorithm = -1;  // infeasible
-    } else {
-      p.key_format = want;
-    }
-    // one super-bucket (no level 2): PACKED degenerates to COMPACT, which then fits
-    if (p.key_format == PDP_KEYS_PACKED && p.super_bits == 0) p.key_format = PDP_KEYS_COMPACT;
-    if (p.algorithm == PDP_ALGO_BUCKETED) p.l1_local = local_fits(p.key_format) ? 1 : 0;
-  }
-  // threshold sieve: tile-local level 1, range merge, whole 64-pid bitmap
-  // words per bucket, and the sieve's larger LDS stage must fit
-  const bool sieve_ok = p.algorithm == PDP_ALGO_BUCKETED && p.l1_local && p.merge == PDP_MERGE_RANGES &&
-                        p.bucket_bits >= 6 && p.key_format != PDP_KEYS_WIDE &&
-                        sieve_lds(p.key_format, kL1Threads, p.n_buckets, true, false) <= kL1LocalLds &&
-                        p.n_tiles * kSieveTileStride < ((int64_t)1 << 32) &&
-                        c->n_privacy_ids < ((int64_t)1 << 32) - 1;  // fix-up lists hold 32-bit ids
-  int t16 = 0;
-  if (sieve_ok && c->sieve > 0) {
-    t16 = c->sieve < kSieveMaxT16 ? c->sieve : kSieveMaxT16;
-  } else if (sieve_ok && c->sieve == 0) {
-    // auto: a privacy id with d distinct partitions has ~d*t candidate pairs;
-    // ask for l0 + 3 sqrt(l0) + 3 of them, assuming d ~ 0.6 rows per id
-    // (C3: 100 rows over Zipf(1.1) keys, t = 0.15); no sieve above t = 0.35
-    const double rows_per_id = (double)c->n_rows / (double)c->n_privacy_ids;
-    const double want = c->l0 + 3.0 * std::sqrt((double)c->l0) + 3.0;
-    const double t = want / (0.6 * rows_per_id);
-    if (t <= 0.35) t16 = (int)std::ceil(t * 65536.0);
-  }
-  p.sieve = t16 > 0 ? t16 : 0;
-  p.band = 0;
-  if (p.sieve) {
-    const int t2 = 2 * p.sieve < kSieveMaxT16 ? 2 * p.sieve : kSieveMaxT16;
-    const bool fits = sieve_lds(p.key_format, kL1Threads, p.n_buckets, true, true) <= kL1LocalLds;
-    // auto: only below t = 1/4 -- there an id short of l0 candidate pairs,
-    // and with it the 8 B/row rescan, is likely (C3: t = 0.154, ~1,600 of 1e7
-    // ids; C2's t = 0.325 leaves none, and the band would only cost level 1
-    // its writes: 1.43 -> 1.52 ms, profiles/r03/ab/ab4_band.txt)
-    const bool want = c->sieve_band > 0 || (c->sieve_band == 0 && p.sieve <= kSieveMaxT16 / 2);
-    if (t2 > p.sieve && fits && want) p.band = t2;
-  }
-  // the sieve's workgroup: 1,024 threads (auto), or on request two 512-thread
-  // ones per CU when their LDS fits (C3: 6.86 vs 6.56 ms, level 1 3.51 vs
-  // 3.44 ms and level 2 0.97 vs 0.80 ms over twice the flush blocks,
-  // profiles/r04/ab/ab1_sieve_threads.txt)
-  p.sieve_threads = kL1Threads;
-  p.hist_u16 = p.l1_local ? (int)l1_hist_u16(p.key_format, p.n_buckets) : 0;
-  if (p.sieve) {
-    const bool band = p.band != 0;
-    p.hist_u16 = sieve_lds(p.key_format, kL1Threads, p.n_buckets, false, band) > kL1LocalLds;
-    const bool u16_2 = sieve_lds(p.key_format, kSieveThreads2, p.n_buckets, false, band) > kSieveLds2;
-    const bool fits2 = sieve_lds(p.key_format, kSieveThreads2, p.n_buckets, u16_2, band) <= kSieveLds2;
-    if (fits2 && c->sieve_threads == kSieveThreads2) {
-      p.sieve_threads = kSieveThreads2;
-      p.hist_u16 = u16_2;
-    }
-  }
-  p.slot_bits = p.sieve_threads == kSieveThreads2 ? SieveShape<kSieveThreads2>::kSlotBits
-                                                   : SieveShape<kL1Threads>::kSlotBits;
-  if (!p.sieve) p.slot_bits = 3;
-  static_assert(kStagesPerTile == 8, "non-sieve level-1 stages per tile = 2^3");
-  p.n_slots1 = p.sieve ? p.n_tiles << p.slot_bits : p.n_stages;
-  // the fix-up per privacy id where a wave's sketches (l0 pair entries, l0 *
-  // linf row entries) fit its LDS slice; keep-all-rows plans (per-pair sums,
-  // not row sketches) and larger bounds keep the fix-up bucket launches
-  p.fix_ids = p.sieve && c->linf > 0 && (int64_t)c->l0 * (1 + (int64_t)c->linf) <= kFixIdsEntries;
-  p.pair_slots = (int64_t)c->l0 << p.bucket_bits;
-  // record segments of the range merge: the main launch's, and one per
-  // fix-up bucket launch (the per-id fix-up lists its pairs flat, after them)
-  p.buckets_out = p.sieve && !p.fix_ids ? (p.band ? 3 : 2) * p.n_buckets : p.n_buckets;
-  p.l2_mult = 1;
-  if (p.sieve) {
-    // expected records of one (group of kL2GroupTiles tiles, super-bucket)
-    const double per_group = (double)kL2GroupTiles * (double)kTileRows * ((double)p.sieve / 65536.0) /
-                             (double)(p.n_supers > 0 ? p.n_supers : 1);
-    int m = (int)(kL2Target / (per_group > 1.0 ? per_group : 1.0));
-    const int m_max = kL2Threads / (kL2GroupTiles << p.slot_bits);  // one slot per level-2 thread
-    const int cap = kSieveL2Groups < m_max ? kSieveL2Groups : m_max;
-    p.l2_mult = m < 1 ? 1 : (m > cap ? cap : m);
-  }
-  if (p.algorithm == PDP_ALGO_BUCKETED) {  // candidate queues (key + row) per wave + pid hashes
-    p.lds_bytes = ((p.lds_bytes + 7) & ~(int64_t)7) + (p.bucket_threads / 64) * kQueueCap * 12;
-    p.lds_bytes += ((int64_t)8 << p.bucket_bits);  // {pid hash, sketch-maximum high half} per pid
-  }
-  if (p.merge == PDP_MERGE_RANGES) {
-    // range r yields ceil(records_r / C) items + 1 sentinel, and a bucket
-    // emits at most l0 * 2^bucket_bits records in all
-    const int64_t recs = p.buckets_out * ((int64_t)c->l0 << p.bucket_bits);
-    p.range_group = kRangeChunk;
-    p.n_groups = recs / kRangeChunk + 2 * (int64_t)p.n_ranges + 1;
-    p.fine_items = p.two_level ? recs / kRangeChunk + p.n_fine + 1 : 0;
-  } else {
-    p.n_ranges = 0;
-    p.range_group = 0;
-    p.n_groups = 0;
-    p.two_level = 0;
-    p.fine_items = 0;
-  }
-  return p;
-}
-
-// kLdsBudget bounds the sketches alone; the pid-hash table (8 bytes per id),
-// the wave queues and the range scratch come on top, and the bucket kernel
-// cannot be launched with more than a workgroup's kLdsLimit: 4,096 ids of 28
-// bytes (l0 = 1, linf = 2) or 2,048 of 60 (l0 = 3, linf = 1) went over it.
-// Halve the bucket until the whole of it fits: lds_bytes is the dynamic
-// request, and the kernel's static LDS (kBucketStaticLds) counts as well --
-// 2,048 ids of 60 bytes under the atomic merge come to exactly kLdsLimit
-// without it.
-Plan make_plan(const pdp_bound_config* c) {
-  Plan p = make_plan_capped(c, 63);
-  while (p.algorithm == PDP_ALGO_BUCKETED && p.lds_bytes + kBucketStaticLds > kLdsLimit && p.bucket_bits > 4)
-    p = make_plan_capped(c, p.bucket_bits - 1);
-  return p;
-}
-
-
-// row stride of the per-tile bucket counts in buckets (KP.cstride): whole
-// 16-byte rows of u16 pairs (tile-local level 1) or u32 counts, so
-// k_gscan_sums reads eight or four buckets per lane
-inline int64_t counts_stride(int64_t n_buckets) { return (n_buckets + 7) & ~(int64_t)7; }
-
-Ws layout(const pdp_bound_config* c, const Plan& p) {
-  Ws w{};
-  uint64_t off = 0;
-  w.err = off;
-  off = align256(off + 16);
-  if (p.algorithm == PDP_ALGO_GLOBAL_SKETCH) {
-    const uint64_t slots = (uint64_t)c->n_privacy_ids * (uint64_t)c->l0;
-    w.sketch = off; off = align256(off + slots * 8);
-    w.cnt = off; off = align256(off + slots * 4);
-    if (c->linf > 0) {
-      w.rows = off; off = align256(off + slots * (uint64_t)c->linf * 8);
-    } else {
-      w.fsum = off; off = align256(off + slots * 8);  // double or int64
-      w.nsum = off; off = align256(off + slots * 8);
-      w.nsum2 = off; off = align256(off + slots * 8);
-    }
-  } else {
-    const uint64_t n_counts = (uint64_t)counts_stride(p.n_buckets) * (uint64_t)p.n_tiles;
-    const uint64_t n_chunks = ((uint64_t)p.n_buckets + kScanChunk - 1) / kScanChunk;
-    const uint64_t n = (uint64_t)c->n_rows;
-    w.counts_tm = off; off = align256(off + n_counts * 4);
-    const bool u16 = p.hist_u16 != 0;
-    if (p.l1_local && u16) { w.counts_tm2 = off; off = align256(off + n_counts * 4); }
-    w.tile_over = off; off = align256(off + (uint64_t)p.n_tiles * 4);
-    w.counts = off; off = align256(off + ((uint64_t)p.n_buckets + 1) * 4);  // bucket starts
-    w.chunk_sums = off; off = align256(off + (n_chunks + 1) * 4);
-    const uint64_t n_sc = ((uint64_t)p.n_tiles + kScanChunkTiles - 1) / kScanChunkTiles;
-    const uint64_t n_grp = ((uint64_t)p.n_tiles + kL2GroupTiles - 1) / kL2GroupTiles;
-    w.csum = off; off = align256(off + n_sc * (uint64_t)p.n_buckets * 4);
-    w.gcur = off; off = align256(off + n_grp * (uint64_t)p.n_buckets * 4);
-    w.super_base = off; off = align256(off + (uint64_t)(p.n_supers + 1) * 4);
-    w.super_tm = off; off = align256(off + (uint64_t)p.n_tiles * p.n_supers * 4);
-    w.super_off = off; off = align256(off + (uint64_t)p.n_tiles * p.n_supers * 4);
-    const bool packed = (p.key_format == PDP_KEYS_PACKED || p.key_format == PDP_KEYS_PACKED_WIDE ||
-                         p.key_format == PDP_KEYS_PACKED64) && p.super_bits > 0;
-    const uint64_t kb1 = p.key_format == PDP_KEYS_COMPACT ? 4 : 8;  // level-1 key
-    const uint64_t kb2 = (p.key_format == PDP_KEYS_WIDE || p.key_format == PDP_KEYS_PACKED_WIDE ||
-                          p.key_format == PDP_KEYS_PACKED64) ? 8 : 4;  // level-2 key
-    const bool rows2 = p.key_format != PDP_KEYS_PACKED64;  // PACKED64: the row rides in the key
-    // level-1 records: stage blocks, or the sieve's per-tile flush blocks
-    const uint64_t n1 = p.sieve ? (uint64_t)p.n_tiles * kSieveTileStride
-                                : (p.l1_local ? (uint64_t)p.n_stages * kL1Rows : n);
-    w.keys1 = off; off = align256(off + n1 * (packed ? 8 : kb1));
-    if (!packed) { w.rows1 = off; off = align256(off + n1 * 4); }
-    if (p.sieve) {  // the fix-up list reuses [keys1, end of rows1), at least 8 B per row
-      if (off - w.keys1 < 8 * n) off = w.keys1 + align256(8 * n);
-      w.fix_rec = w.keys1;
-      w.fix_cap = (off - w.keys1) / 8;
-    }
-    if (p.l1_local) { w.soff = off; off = align256(off + (uint64_t)p.n_slots1 * (p.n_supers + 1) * 2); }
-    if (p.sieve) {
-      const uint64_t ids = (uint64_t)p.n_buckets << p.bucket_bits;
-      w.sbase = off; off = align256(off + (uint64_t)p.n_slots1 * 4);
-      w.unres_bits = off; off = align256(off + ids / 8);
-      w.unres_list = off; off = align256(off + ids * 4);
-      w.sctl = off; off = align256(off + 16);
-      w.fix_cnt = off; off = align256(off + ((uint64_t)p.n_buckets + 1) * 4);
-      w.fix_cur = off; off = align256(off + (uint64_t)p.n_buckets * 4);
-      // listed buckets; per-id fix-up: {bucket, begin, end, id} of every id
-      // over the row cap (their rows are distinct entries of the fix-up list)
-      const uint64_t n_blist = p.fix_ids ? 4 * (w.fix_cap / kFixIdsRowCap + 1) : (uint64_t)p.n_buckets;
-      w.fix_blist = off; off = align256(off + (n_blist + 1) * 4);
-      if (p.fix_ids) {
-        w.id_pos = off; off = align256(off + ids * 4);
-        w.id_seg = off; off = align256(off + ids * 8);
-        if (p.band) { w.id_seg2 = off; off = align256(off + ids * 8); }
-        w.fix_ctl = off; off = align256(off + 16);
-      }
-      if (p.band) {  // the band lists; the second fix-up's unresolved ids and counts
-        w.band = off; off = align256(off + (uint64_t)p.n_tiles * kBandTileStride * 8);
-        w.band_cnt = off; off = align256(off + (uint64_t)p.n_tiles * 4);
-        w.unres2_bits = off; off = align256(off + ids / 8);
-        w.unres2_list = off; off = align256(off + ids * 4);
-        w.sctl2 = w.sctl + 8;  // {count, rows} beside sctl's: pdp_bound_stats_async reads both with one copy
-        w.fix_cnt2 = off; off = align256(off + ((uint64_t)p.n_buckets + 1) * 4);
-        w.fix_cur2 = off; off = align256(off + (uint64_t)p.n_buckets * 4);
-      }
-    }
-    if (p.super_bits > 0) {
-      w.keys2 = off; off = align256(off + n * kb2);
-      if (rows2) { w.rows2 = off; off = align256(off + n * 4); }
-      else w.rows2 = w.keys2;  // unused
-    } else {
-      w.keys2 = w.keys1;
-      w.rows2 = w.rows1;
-    }
-    w.cand_key = off; off = align256(off + n * kb2);
-    w.cand_idx = off; off = align256(off + n * 4);
-    if (p.merge == PDP_MERGE_RANGES) {
-      const uint64_t recs = (uint64_t)(p.buckets_out + (p.fix_ids ? p.n_buckets : 0)) * ((uint64_t)c->l0 << p.bucket_bits);
-      w.runs = off; off = align256(off + (uint64_t)p.buckets_out * (p.n_ranges + 1) * 4);
-      w.rec_key = off; off = align256(off + recs * 8);
-      if (c->flags & (PDP_ACC_SUM | PDP_SUM_PER_PARTITION)) { w.rec_f0 = off; off = align256(off + recs * 8); }
-      if (c->flags & PDP_ACC_NSUM) { w.rec_f1 = off; off = align256(off + recs * 8); }
-      if (c->flags & PDP_ACC_NSUM2) { w.rec_f2 = off; off = align256(off + recs * 8); }
-      w.rr_items = off; off = align256(off + (uint64_t)p.n_groups * 16);
-      w.rr_count = off; off = align256(off + 16);
-      if (p.two_level) {  // fine-range counts, starts, cursors; records re-sorted by fine range
-        const uint64_t nf = (uint64_t)p.n_fine;
-        w.fine_total = off; off = align256(off + (nf + 1) * 4);
-        w.fine_chunks = off; off = align256(off + (uint64_t)scan_chunk_sums_len((int64_t)nf) * 4);
-        w.fine_cur = off; off = align256(off + nf * 4);
-        w.stg_key = off; off = align256(off + recs * 8);
-        if (w.rec_f0) { w.stg_f0 = off; off = align256(off + recs * 8); }
-        if (w.rec_f1) { w.stg_f1 = off; off = align256(off + recs * 8); }
-        if (w.rec_f2) { w.stg_f2 = off; off = align256(off + recs * 8); }
-        w.fine_items = off; off = align256(off + (uint64_t)p.fine_items * 16);
-        w.fine_count = off; off = align256(off + 16);
-        const uint64_t F = (uint64_t)1 << (p.range_bits - kRangeBits);
-        w.item_hist = off; off = align256(off + (uint64_t)p.n_groups * F * 4);
-      }
-    }
-  }
-  w.total = off;
-  return w;
-}
-
-// PDP_DEBUG_CORRUPT_RECORDS deliberately corrupts the level-2 records: only
-// accepted when the process asked for test hooks
-bool test_hooks_enabled() {
-  const char* v = std::getenv("PIPELINEDP_AMD_TEST_HOOKS");
-  return v != nullptr && v[0] == '1';
-}
-
-int validate(const pdp_bound_config* c) {
-  if (c == nullptr) return set_error(PDP_E_INVALID, "config is NULL");
-  if (c->n_rows < 0 || c->n_rows >= ((int64_t)1 << 32))
-    return set_error(PDP_E_INVALID, "n_rows must be in [0, 2^32)");
-  if (c->n_privacy_ids < 1 || c->n_privacy_ids >= ((int64_t)1 << 40))
-    return set_error(PDP_E_INVALID, "n_privacy_ids must be in [1, 2^40)");
-  if (c->n_partitions < 1 || c->n_partitions >= ((int64_t)1 << 32))
-    return set_error(PDP_E_INVALID, "n_partitions must be in [1, 2^32)");
-  if (c->l0 < 0 || c->l0 > PDP_MAX_L0)
-    return set_error(PDP_E_UNSUPPORTED, "l0 out of supported range [0, PDP_MAX_L0]");
-  if (c->linf < 0 || c->linf > PDP_MAX_LINF)
-    return set_error(PDP_E_UNSUPPORTED, "linf out of supported range [0, PDP_MAX_LINF]");
-  if (c->max_contributions < 0 || c->max_contributions > PDP_MAX_CONTRIBUTIONS)
-    return set_error(PDP_E_UNSUPPORTED, "max_contributions out of supported range [0, PDP_MAX_CONTRIBUTIONS]");
-  if (c->value_kind < PDP_VALUE_NONE || c->value_kind > PDP_VALUE_I64)
-    return set_error(PDP_E_INVALID, "bad value_kind");
-  if (c->value_kind != PDP_VALUE_I64 && (c->flags & PDP_SUM_INT))
-    return set_error(PDP_E_INVALID, "PDP_SUM_INT requires int64 values");
-  if (c->flags & PDP_SUM_INT) {
-    // the kernels clip in int64 with (long long)bound, which C++ defines only
-    // for a bound that is an int64: finite, integral, in [-2^63, 2^63)
-    auto is_int64 = [](double b) {
-      return std::isfinite(b) && b == std::floor(b) && b >= -9223372036854775808.0 && b < 9223372036854775808.0;
-    };
-    const bool per_partition = (c->flags & PDP_SUM_PER_PARTITION) != 0;
-    if (per_partition ? !(is_int64(c->min_sum) && is_int64(c->max_sum))
-                      : !(is_int64(c->min_value) && is_int64(c->max_value)))
-      return set_error(PDP_E_UNSUPPORTED, per_partition
-                                              ? "PDP_SUM_INT requires min_sum / max_sum that are int64 values"
-                                              : "PDP_SUM_INT requires min_value / max_value that are int64 values");
-  }
-  if (c->algorithm < PDP_ALGO_AUTO || c->algorithm > PDP_ALGO_PAIR_TABLE)
-    return set_error(PDP_E_INVALID, "bad algorithm");
-  if (c->merge < PDP_MERGE_AUTO || c->merge > PDP_MERGE_RANGES)
-    return set_error(PDP_E_INVALID, "bad merge");
-  if (c->key_format < PDP_KEYS_AUTO || c->key_format > PDP_KEYS_PACKED64)
-    return set_error(PDP_E_INVALID, "bad key_format");
-  if (c->sieve_threads != 0 && c->sieve_threads != kSieveThreads2 && c->sieve_threads != kL1Threads)
-    return set_error(PDP_E_INVALID, "sieve_threads must be 0, 512 or 1024");
-  if (c->bucket_threads != 0 && c->bucket_threads != kBucketThreads / 2 && c->bucket_threads != kBucketThreads)
-    return set_error(PDP_E_INVALID, "bucket_threads must be 0, 512 or 1024");
-  if ((c->flags & PDP_DEBUG_CORRUPT_RECORDS) && !test_hooks_enabled())
-    return set_error(PDP_E_INVALID, "PDP_DEBUG_CORRUPT_RECORDS is a test hook: set PIPELINEDP_AMD_TEST_HOOKS=1");
-  if (pairs_mode(c)) return pairs_validate(c);
-  if (make_plan(c).algorithm < 0)
-    return set_error(PDP_E_UNSUPPORTED, "bucketed algorithm / range merge / compact keys infeasible for this l0/linf/U/P");
-  return PDP_OK;
-}
-
-
-
-KP make_kp(const pdp_bound_config* c, const Plan& p) {
-  KP k;
-  k.n = c->n_rows;
-  k.U = c->n_privacy_ids;
-  k.P = c->n_partitions;
-  k.l0 = c->l0;
-  k.linf = c->linf;
-  k.pk_bits = p.pk_bits;
-  k.bucket_bits = p.bucket_bits;
-  k.super_bits = p.super_bits;
-  k.rand_shift = p.rand_shift;
-  k.n_buckets = p.n_buckets;
-  k.n_supers = p.n_supers;
-  k.n_tiles = p.n_tiles;
-  k.n_ranges = p.n_ranges;
-  k.range_bits = p.range_bits;
-  k.n_fine_ranges = p.n_fine;
-  k.keys_vec = 0;
-  k.n_slots1 = p.n_slots1;
-  k.l2_group_mult = p.l2_mult;
-  k.sieve_t32 = (uint32_t)p.sieve << 16;
-  k.sieve_mark = p.sieve != 0;
-  k.band_t32 = (uint32_t)p.band << 16;
-  k.sieve_emit = p.band != 0;
-  k.slot_bits = p.slot_bits;
-  k.fix_cap = 0;  // set from the layout (Ws.fix_cap) where the fix-up runs
-  k.row_shift = p.pk_bits + p.bucket_bits;
-  k.fix_ids = 0;
-  k.pk_mask = (1ULL << p.pk_bits) - 1;
-  k.seed = c->seed;
-  k.row_seed = derive_row_seed(c->seed);
-  k.row_offset = c->row_offset;
-  k.cstride = counts_stride(p.n_buckets);
-  k.clip = ClipParams{c->min_value, c->max_value, c->middle, c->min_sum, c->max_sum, c->flags};
-  return k;
-}
 
 // ============================================================ GLOBAL path ==
 __global__ void __launch_bounds__(kBlock) k_pair_sketch(KP kp, const int64_t* __restrict__ pid,
@@ -1008,6 +518,9 @@ struct StageLds {
 };
 constexpr int kSmallDest = 256;  // u8 tags; 39.9 KB with compact keys: four workgroups per CU
 
+}  // namespace
+
+// the sizes the planner asks for (declared in pdp_bound_plan.h)
 size_t l1_stage_bytes(int key_format) {
   switch (key_format) {
     case PDP_KEYS_COMPACT: return sizeof(StageLds<L1Key<PDP_KEYS_COMPACT>, kSmallDest, true, kL1Items, kL1Threads>);
@@ -1032,6 +545,11 @@ size_t sieve_stage_bytes(int key_format, int threads) {
   return threads == kSieveThreads2 ? sieve_stage_bytes_t<kSieveThreads2>(key_format)
                                    : sieve_stage_bytes_t<kL1Threads>(key_format);
 }
+int sieve_slot_bits(int threads) {
+  return threads == kSieveThreads2 ? SieveShape<kSieveThreads2>::kSlotBits : SieveShape<kL1Threads>::kSlotBits;
+}
+
+namespace {
 
 // phase 1: histogram + local rank (dest < 0 = drop the row)
 template <typename K, int MAXD, bool ROWS, int N, int TH>
@@ -3267,9 +2785,9 @@ int launch_global_rows(const pdp_bound_config* cfg, const KP& kp, hipStream_t st
   return with_value(cfg->value_kind, cfg->linf == 0, [&](auto vk, auto ka) {
     constexpr bool KA = decltype(ka)::value;
     return launch("k_pair_rows", k_pair_rows<decltype(vk)::value, KA>, dim3(grid_for(kp.n)), dim3(kBlock), 0, st, kp,
-                  pid, pk, value, allowed, (const unsigned long long*)(ws + w.sketch), (unsigned*)(ws + w.cnt),
-                  KA ? nullptr : (unsigned long long*)(ws + w.rows), KA ? (double*)(ws + w.fsum) : nullptr,
-                  KA ? (double*)(ws + w.nsum) : nullptr, KA ? (double*)(ws + w.nsum2) : nullptr);
+                  pid, pk, value, allowed, at<unsigned long long>(ws, w.sketch), at<unsigned>(ws, w.cnt),
+                  KA ? nullptr : at<unsigned long long>(ws, w.rows), KA ? at<double>(ws, w.fsum) : nullptr,
+                  KA ? at<double>(ws, w.nsum) : nullptr, KA ? at<double>(ws, w.nsum2) : nullptr);
   });
 }
 
@@ -3278,15 +2796,11 @@ int launch_global_reduce(const pdp_bound_config* cfg, const KP& kp, hipStream_t 
   return with_value(cfg->value_kind, cfg->linf == 0, [&](auto vk, auto ka) {
     constexpr bool KA = decltype(ka)::value;
     return launch("k_reduce_pairs", k_reduce_pairs<decltype(vk)::value, KA>, dim3(grid_for(kp.U * kp.l0)),
-                  dim3(kBlock), 0, st, kp, value, (const unsigned long long*)(ws + w.sketch),
-                  (const unsigned*)(ws + w.cnt), KA ? nullptr : (const unsigned long long*)(ws + w.rows),
-                  KA ? (const double*)(ws + w.fsum) : nullptr, KA ? (const double*)(ws + w.nsum) : nullptr,
-                  KA ? (const double*)(ws + w.nsum2) : nullptr, acc);
+                  dim3(kBlock), 0, st, kp, value, at<unsigned long long>(ws, w.sketch), at<unsigned>(ws, w.cnt),
+                  KA ? nullptr : at<unsigned long long>(ws, w.rows), KA ? at<double>(ws, w.fsum) : nullptr,
+                  KA ? at<double>(ws, w.nsum) : nullptr, KA ? at<double>(ws, w.nsum2) : nullptr, acc);
   });
 }
-
-int64_t device_cus();  // compute units of the current device
-
 
 // where a bucket launch marks unresolved ids (the main launch: the first
 // bitmap / list / counters; the band's fix-up launch: the second ones, only
@@ -3322,9 +2836,8 @@ int launch_bucket_kernel(const KP& kp, const Plan& p, hipStream_t st, const void
     const int64_t grid = blist != nullptr ? std::min<int64_t>(kp.fix_ids ? 2 * p.n_buckets : p.n_buckets, device_cus())
                                           : p.n_buckets;
     return launch(name, kern, dim3((unsigned)grid), dim3((unsigned)p.bucket_threads), (size_t)p.lds_bytes, st, kp,
-                  (const K*)keys, rows, offsets, value, acc, rec, (K*)(ws + w.cand_key),
-                  (unsigned*)(ws + w.cand_idx), mk.bits, mk.list, mk.sctl, (unsigned*)(ws + w.err), mk.fix_rec,
-                  mk.prev, blist, mk.pos, mk.seg);
+                  (const K*)keys, rows, offsets, value, acc, rec, at<K>(ws, w.cand_key), at<unsigned>(ws, w.cand_idx),
+                  mk.bits, mk.list, mk.sctl, at<unsigned>(ws, w.err), mk.fix_rec, mk.prev, blist, mk.pos, mk.seg);
   });
 }
 
@@ -3343,37 +2856,40 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
                       const uint8_t* allowed, const void* value, const pdp_partition_accumulators& acc, char* ws,
                       const Ws& w) {
   const PairRecords rec = pair_records(ws, w, p);
-  unsigned long long* fix_rec = (unsigned long long*)(ws + w.fix_rec);  // level-1 blocks are dead
-  unsigned* id_pos = p.fix_ids ? (unsigned*)(ws + w.id_pos) : nullptr;
-  unsigned* seg1 = p.fix_ids ? (unsigned*)(ws + w.id_seg) : nullptr;
-  unsigned* seg2 = p.fix_ids && p.band ? (unsigned*)(ws + w.id_seg2) : nullptr;
-  Marks m1{w.unres_bits ? (unsigned*)(ws + w.unres_bits) : nullptr,
-           w.unres_list ? (unsigned*)(ws + w.unres_list) : nullptr, w.sctl ? (unsigned*)(ws + w.sctl) : nullptr,
+  unsigned long long* fix_rec = at<unsigned long long>(ws, w.fix_rec);  // level-1 blocks are dead
+  unsigned* id_pos = at_opt<unsigned>(ws, w.id_pos);  // the three: per-id fix-up only
+  unsigned* seg1 = at_opt<unsigned>(ws, w.id_seg);
+  unsigned* seg2 = at_opt<unsigned>(ws, w.id_seg2);  // ... with the band
+  void* keys2 = at<void>(ws, w.keys2);
+  unsigned* rows2 = at<unsigned>(ws, w.rows2);
+  unsigned* err = at<unsigned>(ws, w.err);
+  Marks m1{at_opt<unsigned>(ws, w.unres_bits), at_opt<unsigned>(ws, w.unres_list), at_opt<unsigned>(ws, w.sctl),
            nullptr, p.band ? fix_rec : nullptr, id_pos, seg1};
-  int rc = launch_bucket_kernel<VK, KA>(kp, p, st, ws + w.keys2, (const unsigned*)(ws + w.rows2),
-                                        (const unsigned*)(ws + w.counts), value, acc, rec, ws, w, "k_bucket_bound", m1);
+  int rc = launch_bucket_kernel<VK, KA>(kp, p, st, keys2, rows2, at<unsigned>(ws, w.counts), value, acc, rec, ws, w,
+                                        "k_bucket_bound", m1);
   if (rc != PDP_OK || !p.sieve) return rc;
   const int64_t n_slots = (int64_t)kp.l0 << kp.bucket_bits;
+  // what both fix-ups launch with: the listed buckets, kernel parameters that
+  // mark as asked and emit nothing, the bucket workgroup halved where `half`
+  unsigned* blist = at<unsigned>(ws, w.fix_blist);
+  auto fix_kp = [&](int mark) { KP kf = kp; kf.sieve_mark = mark; kf.sieve_emit = 0; return kf; };
+  auto fix_plan = [&](bool half) { Plan pf = p; if (half) pf.bucket_threads = kBucketThreads / 2; return pf; };
   // one fix-up: rows listed in fix_rec (sctl[1] of them) -> exact test ->
   // bucket order -> a bucket launch over them into record segment `seg`
   auto fixup = [&](unsigned* bits, unsigned* sctl, unsigned* fix_cnt, unsigned* fix_cur, int seg, const Marks& mk,
                    int mark, const char* name) -> int {
-    unsigned* blist = (unsigned*)(ws + w.fix_blist);
     int r = launch("k_fix_filter", k_fix_filter, dim3(grid_for(kp.n, 1024)), dim3(kBlock), 0, st, kp, bits, sctl,
-                   fix_rec, fix_cnt, (unsigned*)(ws + w.err), blist);
+                   fix_rec, fix_cnt, err, blist);
     if (r != PDP_OK) return r;
-    r = scan_u32(fix_cnt, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);  // -> starts
+    r = scan_u32(fix_cnt, p.n_buckets, at<unsigned>(ws, w.chunk_sums), st);  // -> starts
     if (r != PDP_OK) return r;
     r = with_rec(rec_of(p.key_format), [&](auto kind) {
       constexpr int REC = decltype(kind)::value;
       return launch("k_fix_scatter", k_fix_scatter<REC>, dim3(grid_for(kp.n, 2048)), dim3(kBlock), 0, st, kp, pk,
-                    allowed, fix_rec, sctl, fix_cnt, fix_cur, (RecKey<REC == kRecCompact>*)(ws + w.keys2),
-                    (unsigned*)(ws + w.rows2));
+                    allowed, fix_rec, sctl, fix_cnt, fix_cur, (RecKey<REC == kRecCompact>*)keys2, rows2);
     });
     if (r != PDP_OK) return r;
-    KP kf = kp;
-    kf.sieve_mark = mark;
-    kf.sieve_emit = 0;
+    const KP kf = fix_kp(mark);
     PairRecords fr = rec;
     fr.runs += seg * p.n_buckets;  // column offset (range-major table)
     fr.key += seg * p.n_buckets * n_slots;
@@ -3388,10 +2904,8 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
                fix_cnt, p.merge == PDP_MERGE_RANGES ? fr.runs : nullptr, fr.run_stride, blist,
                mark ? mk.prev : nullptr, mk.bits, mk.list, mk.sctl);
     if (r != PDP_OK) return r;
-    Plan pf = p;
-    if (p.merge != PDP_MERGE_RANGES || p.n_ranges <= kBucketThreads / 2) pf.bucket_threads = kBucketThreads / 2;
-    return launch_bucket_kernel<VK, KA>(kf, pf, st, ws + w.keys2, (const unsigned*)(ws + w.rows2),
-                                        (const unsigned*)fix_cnt, value, acc, fr, ws, w, name, mk, blist);
+    const Plan pf = fix_plan(p.merge != PDP_MERGE_RANGES || p.n_ranges <= kBucketThreads / 2);
+    return launch_bucket_kernel<VK, KA>(kf, pf, st, keys2, rows2, fix_cnt, value, acc, fr, ws, w, name, mk, blist);
   };
   // the same per privacy id (Plan.fix_ids): exact test + rows per id -> id
   // order -> one wave per listed id (`list`, its rows' bounds in `seg`),
@@ -3399,74 +2913,60 @@ int launch_buckets_of(const KP& kp, const Plan& p, hipStream_t st, const int64_t
   // ids over the row cap -> a listed bucket launch (empty unless there is one)
   auto fixup_ids = [&](unsigned* bits, const unsigned* list, unsigned* sctl, unsigned* seg, const Marks& mk, int mark,
                        const char* name) -> int {
-    unsigned* blist = (unsigned*)(ws + w.fix_blist);
-    unsigned* err = (unsigned*)(ws + w.err);
     int r = launch("k_fix_filter", k_fix_id_count, dim3(grid_for(kp.n, 1024)), dim3(kBlock), 0, st, kp, bits, sctl,
                    fix_rec, id_pos, seg, err, blist);
     if (r != PDP_OK) return r;
     r = launch("k_fix_alloc", k_fix_id_alloc, dim3(1), dim3(kBlock), 0, st, sctl, seg);
     if (r != PDP_OK) return r;
-    KP kf = kp;
-    kf.sieve_mark = mark;
-    kf.sieve_emit = 0;
+    KP kf = fix_kp(mark);
     r = with_rec(rec_of(p.key_format), [&](auto kind) {
       constexpr int REC = decltype(kind)::value;
       using K = RecKey<REC == kRecCompact>;
       int r2 = launch("k_fix_scatter", k_fix_id_scatter<REC>, dim3(grid_for(kp.n, 2048)), dim3(kBlock), 0, st, kp, pk,
-                      allowed, fix_rec, sctl, id_pos, seg, (K*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
+                      allowed, fix_rec, sctl, id_pos, seg, (K*)keys2, rows2);
       if (r2 != PDP_OK) return r2;
       const IdMarks im{mk.bits, mk.list, mk.sctl, mk.seg};
       // persistent: four ids per workgroup at a time, up to 8 workgroups per CU
       const int64_t ids = p.n_buckets << p.bucket_bits;
       const int64_t grid = std::min<int64_t>((ids + 3) / 4, 8 * device_cus());
       return launch("k_fix_ids", k_fix_ids<VK, REC>, dim3((unsigned)grid), dim3(kFixIdsThreads), 0, st, kf,
-                    list, sctl, seg, (const K*)(ws + w.keys2), (const unsigned*)(ws + w.rows2), value, rec, im, id_pos,
-                    blist, err);
+                    list, sctl, seg, (const K*)keys2, rows2, value, rec, im, id_pos, blist, err);
     });
     if (r != PDP_OK) return r;
     kf.fix_ids = 1;
-    Plan pf = p;
-    if (p.n_ranges <= kBucketThreads / 2) pf.bucket_threads = kBucketThreads / 2;
-    return launch_bucket_kernel<VK, KA>(kf, pf, st, ws + w.keys2, (const unsigned*)(ws + w.rows2), nullptr, value, acc,
-                                        rec, ws, w, name, mk, blist);
+    const Plan pf = fix_plan(p.n_ranges <= kBucketThreads / 2);
+    return launch_bucket_kernel<VK, KA>(kf, pf, st, keys2, rows2, nullptr, value, acc, rec, ws, w, name, mk, blist);
   };
   auto rescan = [&](const unsigned* bits, const unsigned* list, unsigned* sctl) {
     return launch("k_sieve_rescan", kp.keys_vec ? k_sieve_rescan<true> : k_sieve_rescan<false>, dim3(kRescanBlocks),
                   dim3(kRescanThreads), 0, st, kp, pid, bits, list, sctl, fix_rec);
   };
-  unsigned* sctl = (unsigned*)(ws + w.sctl);
-  unsigned* fix_cnt = (unsigned*)(ws + w.fix_cnt);
-  unsigned* fix_cur = (unsigned*)(ws + w.fix_cur);
   const Marks none{m1.bits, m1.list, m1.sctl, nullptr, nullptr, nullptr, nullptr};
-  if (!p.band) {
-    rc = rescan(m1.bits, m1.list, sctl);
-    if (rc != PDP_OK) return rc;
+  // the second bitmap, list and counters (regions of the band's plans only: else NULL)
+  const Marks m2{at_opt<unsigned>(ws, w.unres2_bits), at_opt<unsigned>(ws, w.unres2_list),
+                 at_opt<unsigned>(ws, w.sctl2), m1.bits, nullptr, id_pos, seg2};
+  // fix-up n of the ids marked in m1 (n = 1) or m2 (n = 2): per id where planned, else by bucket launches
+  auto fix = [&](int n, const Marks& mk, int mark, const char* name) -> int {
+    const Marks& from = n == 1 ? m1 : m2;
     if constexpr (!KA)
-      if (p.fix_ids) return fixup_ids(m1.bits, m1.list, sctl, seg1, none, 0, "k_bucket_fix");
-    return fixup(m1.bits, sctl, fix_cnt, fix_cur, 1, none, 0, "k_bucket_fix");
+      if (p.fix_ids) return fixup_ids(from.bits, from.list, from.sctl, n == 1 ? seg1 : seg2, mk, mark, name);
+    return fixup(from.bits, from.sctl, at<unsigned>(ws, n == 1 ? w.fix_cnt : w.fix_cnt2),
+                 at<unsigned>(ws, n == 1 ? w.fix_cur : w.fix_cur2), n, mk, mark, name);
+  };
+  if (!p.band) {
+    rc = rescan(m1.bits, m1.list, m1.sctl);
+    return rc != PDP_OK ? rc : fix(1, none, 0, "k_bucket_fix");
   }
   // the band: its lists (Bloom filter unless too many ids) -> fix-up launch
   // that marks the ids still unresolved -> their rescan -> a third launch
   rc = launch("k_band_scan", k_band_scan, dim3(kRescanBlocks), dim3(kRescanThreads), 0, st, kp,
-              (const unsigned long long*)(ws + w.band), (const unsigned*)(ws + w.band_cnt), m1.bits, m1.list, sctl,
-              fix_rec);
+              at<unsigned long long>(ws, w.band), at<unsigned>(ws, w.band_cnt), m1.bits, m1.list, m1.sctl, fix_rec);
   if (rc != PDP_OK) return rc;
-  unsigned* sctl2 = (unsigned*)(ws + w.sctl2);
-  const Marks m2{(unsigned*)(ws + w.unres2_bits), (unsigned*)(ws + w.unres2_list), sctl2, m1.bits, nullptr, id_pos, seg2};
-  if constexpr (!KA) {
-    if (p.fix_ids) {
-      rc = fixup_ids(m1.bits, m1.list, sctl, seg1, m2, 1, "k_bucket_fix");
-      if (rc != PDP_OK) return rc;
-      rc = rescan(m2.bits, m2.list, sctl2);
-      if (rc != PDP_OK) return rc;
-      return fixup_ids(m2.bits, m2.list, sctl2, seg2, m2, 0, "k_bucket_fix2");
-    }
-  }
-  rc = fixup(m1.bits, sctl, fix_cnt, fix_cur, 1, m2, 1, "k_bucket_fix");
+  rc = fix(1, m2, 1, "k_bucket_fix");
   if (rc != PDP_OK) return rc;
-  rc = rescan(m2.bits, m2.list, sctl2);
+  rc = rescan(m2.bits, m2.list, m2.sctl);
   if (rc != PDP_OK) return rc;
-  return fixup(m2.bits, sctl2, (unsigned*)(ws + w.fix_cnt2), (unsigned*)(ws + w.fix_cur2), 2, m2, 0, "k_bucket_fix2");
+  return fix(2, m2, 0, "k_bucket_fix2");
 }
 
 int launch_buckets(int value_kind, bool keep_all, const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid,
@@ -3485,8 +2985,8 @@ int launch_scatter(const KP& kp, const Plan& p, hipStream_t st, const int64_t* p
   using K1 = L1Key<FMT>;
   using K2 = L2Key<FMT>;
   constexpr bool ROWS1 = FMT != PDP_KEYS_PACKED;
-  K1* keys1 = (K1*)(ws + w.keys1);
-  unsigned* rows1 = ROWS1 ? (unsigned*)(ws + w.rows1) : nullptr;
+  K1* keys1 = at<K1>(ws, w.keys1);
+  unsigned* rows1 = ROWS1 ? at<unsigned>(ws, w.rows1) : nullptr;
   int rc = launch_big_lds("k_scatter_l1", k_scatter_l1<FMT>, dim3((unsigned)p.n_tiles), dim3(kL1Threads),
                           sizeof(StageLds<K1, kSmallDest, ROWS1, kL1Items, kL1Threads>), st, kp, pid, pk, allowed,
                           super_off, super_base, keys1, rows1, err);
@@ -3497,21 +2997,8 @@ int launch_scatter(const KP& kp, const Plan& p, hipStream_t st, const int64_t* p
   const size_t lds2 = small ? sizeof(StageLds<K2, kSmallDest, true, kL2Items, kL2Threads>)
                             : sizeof(StageLds<K2, kMaxDest, true, kL2Items, kL2Threads>);
   return launch_big_lds("k_scatter_l2", l2, dim3((unsigned)n_grp, (unsigned)p.n_supers), dim3(kL2Threads), lds2, st,
-                        kp, super_base, super_off, bucket_start, gcur, keys1, rows1, (K2*)(ws + w.keys2),
-                        (unsigned*)(ws + w.rows2));
-}
-
-// compute units of the current device (cached per device)
-int64_t device_cus() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
+                        kp, super_base, super_off, bucket_start, gcur, keys1, rows1, at<K2>(ws, w.keys2),
+                        at<unsigned>(ws, w.rows2));
 }
 
 // The small control regions a bounding call starts from (error word, the
@@ -3539,6 +3026,44 @@ int launch_fills(const Fills& f, hipStream_t st) {
                 0, st, f);
 }
 
+// test hook (tools/l1_probe.py): level 1 alone, timed by the profiler;
+// nothing downstream reads what it wrote
+bool stop_after_l1() { return test_hooks_enabled() && std::getenv("PIPELINEDP_AMD_STOP_AFTER_L1") != nullptr; }
+
+// The per-tile bucket counts (counts_tm) -> rows per bucket -> level-2
+// cursors at the tile groups (gcur) -> bucket starts (counts, scanned in
+// place).  `local`: the counts of tile-local level 1 (u16 halves in counts_tm
+// and counts_tm2 or u32, less the tiles in tile_over; eight buckets per lane),
+// whose group sums give the cursors in one pass over the counts; else u32
+// counts of k_part_hist, four per lane, and the cursors, which only a second
+// level reads, by k_gscan_cursors.
+int launch_bucket_starts(const KP& kp, const Plan& p, hipStream_t st, char* ws, const Ws& w, bool local) {
+  const unsigned* counts_tm = at<unsigned>(ws, w.counts_tm);
+  unsigned* counts = at<unsigned>(ws, w.counts);
+  unsigned* csum = at<unsigned>(ws, w.csum);
+  unsigned* gcur = at<unsigned>(ws, w.gcur);
+  const int64_t n_sc = (p.n_tiles + kScanChunkTiles - 1) / kScanChunkTiles;
+  const int64_t per_block = local ? 512 : 256;  // buckets of a k_gscan_sums workgroup: eight or four per lane
+  int rc = launch("k_gscan_sums", local ? k_gscan_sums<true> : k_gscan_sums<false>,
+                  dim3((unsigned)((p.n_buckets + per_block - 1) / per_block), (unsigned)n_sc), dim3(64 * kScanWaves), 0,
+                  st, counts_tm, local ? at_opt<unsigned>(ws, w.counts_tm2) : nullptr,
+                  local ? at<unsigned>(ws, w.tile_over) : nullptr, p.n_tiles, p.n_buckets, kp.cstride, csum,
+                  local ? gcur : nullptr);
+  if (rc != PDP_OK) return rc;
+  rc = launch("k_gscan_chunks", k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc,
+              p.n_buckets, counts);
+  if (rc != PDP_OK) return rc;
+  if (local) {
+    rc = launch("k_gscan_groups", k_gscan_groups, dim3(grid_for(n_sc * p.n_buckets, (int64_t)1 << 30)), dim3(kBlock), 0,
+                st, csum, p.n_tiles, p.n_buckets, gcur);
+  } else if (p.super_bits > 0) {
+    rc = launch("k_gscan_cursors", k_gscan_cursors, dim3((unsigned)((p.n_buckets + 63) / 64), (unsigned)n_sc),
+                dim3(64 * kScanWaves), 0, st, counts_tm, nullptr, p.n_tiles, p.n_buckets, kp.cstride, csum, gcur);
+  }
+  if (rc != PDP_OK) return rc;
+  return scan_u32(counts, p.n_buckets, at<unsigned>(ws, w.chunk_sums), st);
+}
+
 // tile-local level 1 -> level-2 cursors and bucket starts -> tile-local level 2
 template <int FMT>
 int launch_local_fmt(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
@@ -3546,15 +3071,14 @@ int launch_local_fmt(const KP& kp, const Plan& p, hipStream_t st, const int64_t*
   using K1 = L1Key<FMT>;
   using K2 = L2Key<FMT>;
   constexpr bool ROWS1 = !kPackedL1<FMT>;
-  unsigned* counts_tm = (unsigned*)(ws + w.counts_tm);
+  unsigned* counts_tm = at<unsigned>(ws, w.counts_tm);
   const bool u16 = p.hist_u16 != 0;
-  unsigned* counts_tm2 = u16 ? (unsigned*)(ws + w.counts_tm2) : nullptr;
-  unsigned* counts = (unsigned*)(ws + w.counts);
-  uint16_t* soff = (uint16_t*)(ws + w.soff);
-  unsigned* tile_over = (unsigned*)(ws + w.tile_over);  // all ones (k_fill) unless a tile's rows are all one bucket's
-  unsigned* sbase = p.sieve ? (unsigned*)(ws + w.sbase) : nullptr;
-  K1* keys1 = (K1*)(ws + w.keys1);
-  unsigned* rows1 = ROWS1 ? (unsigned*)(ws + w.rows1) : nullptr;
+  unsigned* counts_tm2 = at_opt<unsigned>(ws, w.counts_tm2);  // the u16 counts' second halves
+  uint16_t* soff = at<uint16_t>(ws, w.soff);
+  unsigned* tile_over = at<unsigned>(ws, w.tile_over);  // all ones (k_fill) unless a tile's rows are all one bucket's
+  unsigned* sbase = at_opt<unsigned>(ws, w.sbase);      // the sieve's
+  K1* keys1 = at<K1>(ws, w.keys1);
+  unsigned* rows1 = ROWS1 ? at<unsigned>(ws, w.rows1) : nullptr;
   if constexpr (FMT != PDP_KEYS_WIDE) {
     if (p.sieve) {
       const int th = p.sieve_threads;
@@ -3574,19 +3098,15 @@ int launch_local_fmt(const KP& kp, const Plan& p, hipStream_t st, const int64_t*
       int64_t grid1 = std::min<int64_t>(p.n_tiles, per_cu * device_cus());
       // test hook: fewer workgroups, so that each loops over several tiles
       // (the cross-tile prefetch and the per-tile LDS reset) at test sizes
-      if (test_hooks_enabled()) {
-        const char* g = std::getenv("PIPELINEDP_AMD_L1_GRID");
-        const long long v = g != nullptr ? std::atoll(g) : 0;
-        if (v > 0 && v < grid1) grid1 = v;
-      }
+      if (const long long v = test_hook("PIPELINEDP_AMD_L1_GRID"); v > 0 && v < grid1) grid1 = v;
       rc = launch("k_sieve_l1", l1, dim3((unsigned)grid1), dim3(th), lds1, st, kp, pid, pk, allowed, counts_tm,
-                  counts_tm2, soff, sbase, keys1, rows1, err, p.band ? (unsigned long long*)(ws + w.band) : nullptr,
-                  p.band ? (unsigned*)(ws + w.band_cnt) : nullptr, tile_over);
+                  counts_tm2, soff, sbase, keys1, rows1, err, at_opt<unsigned long long>(ws, w.band),
+                  at_opt<unsigned>(ws, w.band_cnt), tile_over);
       if (rc != PDP_OK) return rc;
     }
   }
   if ((kp.clip.flags & PDP_PROBE_LEVEL1) && p.sieve) return PDP_OK;  // placement probe: level 1 only
-  if (test_hooks_enabled() && std::getenv("PIPELINEDP_AMD_STOP_AFTER_L1") != nullptr && p.sieve) return PDP_OK;
+  if (stop_after_l1() && p.sieve) return PDP_OK;
   int rc = PDP_OK;
   if (!p.sieve) {
     const size_t lds1 = (l1_stage_bytes(FMT) + 7) / 8 * 8 + (size_t)l1_hist_bytes(p.n_buckets, u16);
@@ -3599,21 +3119,7 @@ int launch_local_fmt(const KP& kp, const Plan& p, hipStream_t st, const int64_t*
     if (rc != PDP_OK) return rc;
     if (kp.clip.flags & PDP_PROBE_LEVEL1) return PDP_OK;  // placement probe: level 1 only
   }
-  const int64_t n_bblk8 = (p.n_buckets + 511) / 512;  // k_gscan_sums<true>: eight buckets per lane
-  const int64_t n_sc = (p.n_tiles + kScanChunkTiles - 1) / kScanChunkTiles;
-  unsigned* csum = (unsigned*)(ws + w.csum);
-  unsigned* gcur = (unsigned*)(ws + w.gcur);
-  rc = launch("k_gscan_sums", k_gscan_sums<true>, dim3((unsigned)n_bblk8, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
-              counts_tm, counts_tm2, tile_over, p.n_tiles, p.n_buckets, kp.cstride, csum, gcur);
-  if (rc != PDP_OK) return rc;
-  rc = launch("k_gscan_chunks", k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc,
-              p.n_buckets, counts);
-  if (rc != PDP_OK) return rc;
-  // level-2 cursors from the group sums (one pass over counts_tm in all)
-  rc = launch("k_gscan_groups", k_gscan_groups, dim3(grid_for(n_sc * p.n_buckets, (int64_t)1 << 30)), dim3(kBlock), 0,
-              st, csum, p.n_tiles, p.n_buckets, gcur);
-  if (rc != PDP_OK) return rc;
-  rc = scan_u32(counts, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);
+  rc = launch_bucket_starts(kp, p, st, ws, w, true);
   if (rc != PDP_OK) return rc;
   const int64_t n_grp = (p.n_tiles + kL2GroupTiles - 1) / kL2GroupTiles;
   const bool small = ((int64_t)1 << p.super_bits) <= kSmallDest;
@@ -3622,8 +3128,9 @@ int launch_local_fmt(const KP& kp, const Plan& p, hipStream_t st, const int64_t*
                             : sizeof(StageLds<K2, kMaxDest, kL2RowArray<FMT>, l2_items<FMT>(), kL2Threads>);
   const int64_t n_mgrp = (n_grp + kp.l2_group_mult - 1) / kp.l2_group_mult;  // tile groups per workgroup
   const int64_t n_blk = (n_mgrp + 7) / 8 * 8 * p.n_supers;  // k_scatter_l2_local maps ids to (group, super)
-  return launch_big_lds("k_scatter_l2", l2, dim3((unsigned)n_blk), dim3(kL2Threads), lds2, st, kp, soff, sbase, counts,
-                        gcur, keys1, rows1, (K2*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
+  return launch_big_lds("k_scatter_l2", l2, dim3((unsigned)n_blk), dim3(kL2Threads), lds2, st, kp, soff, sbase,
+                        at<unsigned>(ws, w.counts), at<unsigned>(ws, w.gcur), keys1, rows1, at<K2>(ws, w.keys2),
+                        at<unsigned>(ws, w.rows2));
 }
 
 int launch_local(const KP& kp, const Plan& p, hipStream_t st, const int64_t* pid, const int64_t* pk,
@@ -3656,10 +3163,11 @@ __global__ void __launch_bounds__(kBlock) k_debug_corrupt(KP kp, const unsigned*
 }
 
 int launch_debug_corrupt(const KP& kp, const Plan& p, hipStream_t st, char* ws, const Ws& w) {
+  if (!(kp.clip.flags & PDP_DEBUG_CORRUPT_RECORDS)) return PDP_OK;  // (kp.clip.flags: the config's)
   return with_rec(rec_of(p.key_format), [&](auto rec) {
     constexpr int REC = decltype(rec)::value;
-    return launch(nullptr, k_debug_corrupt<REC>, dim3(64), dim3(kBlock), 0, st, kp, (const unsigned*)(ws + w.counts),
-                  (RecKey<REC == kRecCompact>*)(ws + w.keys2), (unsigned*)(ws + w.rows2));
+    return launch(nullptr, k_debug_corrupt<REC>, dim3(64), dim3(kBlock), 0, st, kp, at<unsigned>(ws, w.counts),
+                  at<RecKey<REC == kRecCompact>>(ws, w.keys2), at<unsigned>(ws, w.rows2));
   });
 }
 
@@ -3667,61 +3175,44 @@ int launch_debug_corrupt(const KP& kp, const Plan& p, hipStream_t st, char* ws, 
 // (plans whose tile-local level 1 does not fit)
 int launch_offsets(const KP& kp, const Plan& p, hipStream_t st, const int64_t* privacy_id,
                    const int64_t* partition_key, const uint8_t* pk_allowed, char* ws, const Ws& w, unsigned* err) {
-  unsigned* counts = (unsigned*)(ws + w.counts);
-  unsigned* counts_tm = (unsigned*)(ws + w.counts_tm);
-  unsigned* super_tm = (unsigned*)(ws + w.super_tm);
-  unsigned* super_off = (unsigned*)(ws + w.super_off);
+  unsigned* counts = at<unsigned>(ws, w.counts);
+  unsigned* super_tm = at<unsigned>(ws, w.super_tm);
+  unsigned* super_off = at<unsigned>(ws, w.super_off);
   int rc = launch_big_lds("k_part_hist", k_part_hist, dim3((unsigned)p.n_tiles), dim3(kPartThreads),
-                          (size_t)p.n_buckets * 4, st, kp, privacy_id, counts_tm, super_tm, err);
+                          (size_t)p.n_buckets * 4, st, kp, privacy_id, at<unsigned>(ws, w.counts_tm), super_tm, err);
   if (rc != PDP_OK) return rc;
   rc = launch("k_super_scan", k_super_scan, dim3((unsigned)p.n_supers), dim3(kBlock), 0, st, kp, super_tm, super_off);
   if (rc != PDP_OK) return rc;
   // rows per bucket (and, with two levels, the level-2 cursors at tile-group starts)
-  const int64_t n_bblk = (p.n_buckets + 63) / 64;
-  const int64_t n_bblk4 = (p.n_buckets + 255) / 256;
-  const int64_t n_sc = (p.n_tiles + kScanChunkTiles - 1) / kScanChunkTiles;
-  unsigned* csum = (unsigned*)(ws + w.csum);
-  unsigned* gcur = (unsigned*)(ws + w.gcur);
-  rc = launch("k_gscan_sums", k_gscan_sums<false>, dim3((unsigned)n_bblk4, (unsigned)n_sc), dim3(64 * kScanWaves), 0,
-              st, counts_tm, nullptr, nullptr, p.n_tiles, p.n_buckets, kp.cstride, csum, nullptr);
+  rc = launch_bucket_starts(kp, p, st, ws, w, false);
   if (rc != PDP_OK) return rc;
-  rc = launch("k_gscan_chunks", k_gscan_chunks, dim3(grid_for(p.n_buckets)), dim3(kBlock), 0, st, csum, n_sc,
-              p.n_buckets, counts);
-  if (rc != PDP_OK) return rc;
-  if (p.super_bits > 0) {
-    rc = launch("k_gscan_cursors", k_gscan_cursors, dim3((unsigned)n_bblk, (unsigned)n_sc), dim3(64 * kScanWaves), 0, st,
-                counts_tm, nullptr, p.n_tiles, p.n_buckets, kp.cstride, csum, gcur);
-    if (rc != PDP_OK) return rc;
-  }
-  rc = scan_u32(counts, p.n_buckets, (unsigned*)(ws + w.chunk_sums), st);
-  if (rc != PDP_OK) return rc;
-  unsigned* super_base = (unsigned*)(ws + w.super_base);
+  unsigned* super_base = at<unsigned>(ws, w.super_base);
   rc = launch("k_super_bases", k_super_bases, dim3(grid_for(p.n_supers + 1)), dim3(kBlock), 0, st, kp, counts,
               super_base);
   if (rc != PDP_OK) return rc;
   // three formats only: PACKED_WIDE and PACKED64 are planned with tile-local level 1 alone
   auto scatter = [&](auto fmt) {
     return launch_scatter<decltype(fmt)::value>(kp, p, st, privacy_id, partition_key, pk_allowed, super_off,
-                                                super_base, counts, gcur, ws, w, err);
+                                                super_base, counts, at<unsigned>(ws, w.gcur), ws, w, err);
   };
   if (p.key_format == PDP_KEYS_COMPACT) return scatter(std::integral_constant<int, PDP_KEYS_COMPACT>{});
   if (p.key_format == PDP_KEYS_PACKED) return scatter(std::integral_constant<int, PDP_KEYS_PACKED>{});
   return scatter(std::integral_constant<int, PDP_KEYS_WIDE>{});
 }
 
-int check_ws(const pdp_bound_config* cfg, const void* workspace, uint64_t workspace_bytes, Plan* p, Ws* w) {
-  const int rc = validate(cfg);
-  if (rc != PDP_OK) return rc;
-  if (pairs_mode(cfg)) {
-    if (workspace == nullptr || workspace_bytes < pairs_workspace_bytes(cfg))
-      return set_error(PDP_E_WORKSPACE, "workspace too small (see pdp_bound_workspace_bytes)");
-    return PDP_OK;
-  }
-  *p = make_plan(cfg);
-  *w = layout(cfg, *p);
-  if (workspace == nullptr || workspace_bytes < w->total)
-    return set_error(PDP_E_WORKSPACE, "workspace too small (see pdp_bound_workspace_bytes)");
+// the value column against the config (pdp_bound_contributions, pdp_reduce_partitions)
+int check_value_args(const pdp_bound_config* cfg, const void* value) {
+  if (cfg->value_kind == PDP_VALUE_NONE &&
+      (cfg->flags & (PDP_ACC_SUM | PDP_ACC_NSUM | PDP_ACC_NSUM2 | PDP_SUM_PER_PARTITION)))
+    return set_error(PDP_E_INVALID, "value sums requested without a value column");
+  if (cfg->value_kind != PDP_VALUE_NONE && cfg->n_rows > 0 && value == nullptr)
+    return set_error(PDP_E_INVALID, "value column is NULL");
   return PDP_OK;
+}
+
+// the call ran the bucketed path, so the workspace holds its counters (`p` is set only outside pairs mode)
+bool ran_bucketed(const pdp_bound_config* cfg, const Plan& p) {
+  return !pairs_mode(cfg) && p.algorithm == PDP_ALGO_BUCKETED && cfg->n_rows > 0;
 }
 
 }  // namespace
@@ -3730,45 +3221,6 @@ int check_ws(const pdp_bound_config* cfg, const void* workspace, uint64_t worksp
 using namespace pdp;
 
 extern "C" {
-
-int pdp_bound_plan(const pdp_bound_config* cfg, pdp_bound_plan_info* info) {
-  const int rc = validate(cfg);
-  if (rc != PDP_OK) return rc;
-  if (info == nullptr) return set_error(PDP_E_INVALID, "info is NULL");
-  if (pairs_mode(cfg)) {
-    *info = pdp_bound_plan_info{};
-    info->algorithm = PDP_ALGO_PAIR_TABLE;
-    info->pk_bits = bits_for(cfg->n_partitions);
-    return PDP_OK;
-  }
-  const Plan p = make_plan(cfg);
-  info->algorithm = p.algorithm;
-  info->bucket_bits = p.bucket_bits;
-  info->rand_shift = p.rand_shift;
-  info->pk_bits = p.pk_bits;
-  info->n_buckets = p.algorithm == PDP_ALGO_BUCKETED ? p.n_buckets : 0;
-  info->n_tiles = p.n_tiles;
-  info->lds_bytes = p.algorithm == PDP_ALGO_BUCKETED ? p.lds_bytes : 0;
-  info->merge = p.merge;
-  info->n_ranges = p.n_ranges;
-  info->range_group = p.range_group;
-  info->key_format = p.key_format;
-  info->sieve = p.sieve;
-  info->band = p.band;
-  info->sieve_threads = p.sieve ? p.sieve_threads : 0;
-  info->bucket_threads = p.bucket_threads;
-  info->hist_u16 = p.algorithm == PDP_ALGO_BUCKETED && p.l1_local ? p.hist_u16 : 0;
-  info->fix_ids = p.algorithm == PDP_ALGO_BUCKETED ? p.fix_ids : 0;
-  return PDP_OK;
-}
-
-int pdp_bound_workspace_bytes(const pdp_bound_config* cfg, uint64_t* bytes) {
-  const int rc = validate(cfg);
-  if (rc != PDP_OK) return rc;
-  if (bytes == nullptr) return set_error(PDP_E_INVALID, "bytes is NULL");
-  *bytes = pairs_mode(cfg) ? pairs_workspace_bytes(cfg) : layout(cfg, make_plan(cfg)).total;
-  return PDP_OK;
-}
 
 int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_id, const int64_t* partition_key,
                             const void* value, const uint8_t* pk_allowed, void* workspace,
@@ -3779,11 +3231,7 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
   if (rc != PDP_OK) return rc;
   if (cfg->n_rows > 0 && (partition_key == nullptr || (privacy_id == nullptr && !cfg->rows_are_units)))
     return set_error(PDP_E_INVALID, "key columns are NULL");
-  if (cfg->value_kind != PDP_VALUE_NONE && cfg->n_rows > 0 && value == nullptr)
-    return set_error(PDP_E_INVALID, "value column is NULL");
-  if (cfg->value_kind == PDP_VALUE_NONE &&
-      (cfg->flags & (PDP_ACC_SUM | PDP_ACC_NSUM | PDP_ACC_NSUM2 | PDP_SUM_PER_PARTITION)))
-    return set_error(PDP_E_INVALID, "value sums requested without a value column");
+  if (const int rcv = check_value_args(cfg, value); rcv != PDP_OK) return rcv;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   if (pairs_mode(cfg)) return pairs_bound(cfg, privacy_id, partition_key, value, pk_allowed, ws, st);
@@ -3792,35 +3240,31 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
   kp.fix_cap = (int64_t)w.fix_cap;
   // test hook: a smaller fix-up list region, so that the guard of its writes
   // and error bit 1 can be exercised (the real region cannot overflow)
-  if (test_hooks_enabled()) {
-    const char* fc = std::getenv("PIPELINEDP_AMD_FIX_CAP");
-    const long long v = fc != nullptr ? std::atoll(fc) : 0;
-    if (v > 0 && v < kp.fix_cap) kp.fix_cap = v;
-  }
-  unsigned* err = (unsigned*)(ws + w.err);
+  if (const long long v = test_hook("PIPELINEDP_AMD_FIX_CAP"); v > 0 && v < kp.fix_cap) kp.fix_cap = v;
+  unsigned* err = at<unsigned>(ws, w.err);
   if (p.algorithm != PDP_ALGO_BUCKETED || cfg->n_rows == 0) PDP_HIP_CHECK(hipMemsetAsync(err, 0, 16, st));
   if (p.algorithm == PDP_ALGO_GLOBAL_SKETCH) {
     const uint64_t slots = (uint64_t)cfg->n_privacy_ids * (uint64_t)cfg->l0;
-    PDP_HIP_CHECK(hipMemsetAsync(ws + w.sketch, 0xFF, slots * 8, st));
-    PDP_HIP_CHECK(hipMemsetAsync(ws + w.cnt, 0, slots * 4, st));
-    if (cfg->linf > 0) PDP_HIP_CHECK(hipMemsetAsync(ws + w.rows, 0xFF, slots * (uint64_t)cfg->linf * 8, st));
-    else PDP_HIP_CHECK(hipMemsetAsync(ws + w.fsum, 0, w.total - w.fsum, st));
+    unsigned long long* sketch = at<unsigned long long>(ws, w.sketch);
+    PDP_HIP_CHECK(hipMemsetAsync(sketch, 0xFF, slots * 8, st));
+    PDP_HIP_CHECK(hipMemsetAsync(at<unsigned>(ws, w.cnt), 0, slots * 4, st));
+    if (cfg->linf > 0) PDP_HIP_CHECK(hipMemsetAsync(at<void>(ws, w.rows), 0xFF, slots * (uint64_t)cfg->linf * 8, st));
+    else PDP_HIP_CHECK(hipMemsetAsync(at<void>(ws, w.fsum), 0, w.total - w.fsum, st));
     if (cfg->n_rows == 0) return PDP_OK;
     rc = launch("k_pair_sketch", k_pair_sketch, dim3(grid_for(cfg->n_rows)), dim3(kBlock), 0, st, kp, privacy_id,
-                partition_key, pk_allowed, (unsigned long long*)(ws + w.sketch), err);
+                partition_key, pk_allowed, sketch, err);
     if (rc != PDP_OK) return rc;
     return launch_global_rows(cfg, kp, st, privacy_id, partition_key, value, pk_allowed, ws, w);
   }
   // bucketed: histogram -> transpose -> scan -> cursors -> scatter (1 or 2 levels)
-  unsigned* counts = (unsigned*)(ws + w.counts);  // rows per bucket -> bucket starts
-  if (cfg->n_rows == 0) {
-    PDP_HIP_CHECK(hipMemsetAsync(counts, 0, (p.n_buckets + 1) * 4, st));
+  if (cfg->n_rows == 0) {  // rows per bucket -> bucket starts
+    PDP_HIP_CHECK(hipMemsetAsync(at<unsigned>(ws, w.counts), 0, (p.n_buckets + 1) * 4, st));
     return PDP_OK;
   }
   {  // the control regions: one k_fill launch
     Fills f{};
     auto add = [&](uint64_t off, int64_t words, unsigned v) {
-      f.p[f.k] = (unsigned*)(ws + off);
+      f.p[f.k] = at<unsigned>(ws, off);
       f.n[f.k] = words;
       f.v[f.k] = v;
       ++f.k;
@@ -3840,24 +3284,18 @@ int pdp_bound_contributions(const pdp_bound_config* cfg, const int64_t* privacy_
       add(w.fix_ctl, 4, 0u);
       if (p.band) add(w.unres2_bits, (p.n_buckets << p.bucket_bits) / 32, 0u);
     }
-    const int rcf = launch_fills(f, st);
-    if (rcf != PDP_OK) return rcf;
+    if (const int rcf = launch_fills(f, st); rcf != PDP_OK) return rcf;
   }
-  int rc2 = PDP_OK;
-  if (p.l1_local) rc2 = launch_local(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
-  else rc2 = launch_offsets(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
+  int rc2 = p.l1_local ? launch_local(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err)
+                       : launch_offsets(kp, p, st, privacy_id, partition_key, pk_allowed, ws, w, err);
   if (rc2 != PDP_OK) return rc2;
   if (cfg->flags & PDP_PROBE_LEVEL1) return PDP_OK;  // placement probe: level 1 only
-  // test hook (tools/l1_probe.py): level 1 alone, timed by the profiler;
-  // nothing downstream reads what it wrote
-  if (test_hooks_enabled() && std::getenv("PIPELINEDP_AMD_STOP_AFTER_L1") != nullptr) return PDP_OK;
+  if (stop_after_l1()) return PDP_OK;
   // PDP_MERGE_ATOMIC: the bucket kernel adds into the accumulators, so it
   // runs in pdp_reduce_partitions; PDP_MERGE_RANGES: all sampling runs here
   if (p.merge != PDP_MERGE_RANGES) return PDP_OK;
-  if (cfg->flags & PDP_DEBUG_CORRUPT_RECORDS) {
-    rc2 = launch_debug_corrupt(kp, p, st, ws, w);
-    if (rc2 != PDP_OK) return rc2;
-  }
+  rc2 = launch_debug_corrupt(kp, p, st, ws, w);
+  if (rc2 != PDP_OK) return rc2;
   const pdp_partition_accumulators none{};
   return launch_buckets(cfg->value_kind, cfg->linf == 0, kp, p, st, privacy_id, partition_key, pk_allowed, value,
                         none, ws, w);
@@ -3873,17 +3311,17 @@ int pdp_bound_stats_read(const pdp_bound_config* cfg, const void* workspace, uin
   *out = pdp_bound_stats{};
   hipStream_t st = (hipStream_t)stream;
   const char* ws = (const char*)workspace;
-  PDP_HIP_CHECK(hipMemcpyAsync(&out->error_flags, ws + w.err, 4, hipMemcpyDeviceToHost, st));
+  PDP_HIP_CHECK(hipMemcpyAsync(&out->error_flags, at<unsigned>(ws, w.err), 4, hipMemcpyDeviceToHost, st));
   unsigned rows = 0, ctl[2] = {0, 0};
-  const bool bucketed = !pairs_mode(cfg) && p.algorithm == PDP_ALGO_BUCKETED && cfg->n_rows > 0;
-  if (bucketed) PDP_HIP_CHECK(hipMemcpyAsync(&rows, ws + w.counts + (uint64_t)p.n_buckets * 4, 4, hipMemcpyDeviceToHost, st));
-  if (bucketed && p.sieve) PDP_HIP_CHECK(hipMemcpyAsync(ctl, ws + w.sctl, 8, hipMemcpyDeviceToHost, st));
+  const bool bucketed = ran_bucketed(cfg, p);
+  if (bucketed) PDP_HIP_CHECK(hipMemcpyAsync(&rows, at<unsigned>(ws, w.counts) + p.n_buckets, 4, hipMemcpyDeviceToHost, st));
+  if (bucketed && p.sieve) PDP_HIP_CHECK(hipMemcpyAsync(ctl, at<unsigned>(ws, w.sctl), 8, hipMemcpyDeviceToHost, st));
   unsigned ctl2[2] = {0, 0};
   std::vector<unsigned> bc;
   if (bucketed && p.band) {
-    PDP_HIP_CHECK(hipMemcpyAsync(ctl2, ws + w.sctl2, 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipMemcpyAsync(ctl2, at<unsigned>(ws, w.sctl2), 8, hipMemcpyDeviceToHost, st));
     bc.resize((size_t)p.n_tiles);
-    PDP_HIP_CHECK(hipMemcpyAsync(bc.data(), ws + w.band_cnt, (size_t)p.n_tiles * 4, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipMemcpyAsync(bc.data(), at<unsigned>(ws, w.band_cnt), (size_t)p.n_tiles * 4, hipMemcpyDeviceToHost, st));
   }
   PDP_HIP_CHECK(hipStreamSynchronize(st));
   out->rows_partitioned = rows;
@@ -3906,11 +3344,12 @@ int pdp_bound_stats_async(const pdp_bound_config* cfg, const void* workspace, ui
   if (rc != PDP_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const char* ws = (const char*)workspace;
-  const bool bucketed = !pairs_mode(cfg) && p.algorithm == PDP_ALGO_BUCKETED && cfg->n_rows > 0;
+  const bool bucketed = ran_bucketed(cfg, p);
   if (!(bucketed && p.sieve)) out[0] = out[1] = 0;
   if (!(bucketed && p.band)) out[2] = out[3] = 0;
   // sctl2 = sctl + 8 bytes (layout): one copy of both counter pairs
-  if (bucketed && p.sieve) PDP_HIP_CHECK(hipMemcpyAsync(out, ws + w.sctl, p.band ? 16 : 8, hipMemcpyDeviceToHost, st));
+  if (bucketed && p.sieve)
+    PDP_HIP_CHECK(hipMemcpyAsync(out, at<unsigned>(ws, w.sctl), p.band ? 16 : 8, hipMemcpyDeviceToHost, st));
   return PDP_OK;
 }
 
@@ -3928,11 +3367,7 @@ int pdp_reduce_partitions(const pdp_bound_config* cfg, const void* value, void* 
     return set_error(PDP_E_INVALID, "accumulators.normalized_sum is required by flags");
   if ((cfg->flags & PDP_ACC_NSUM2) && acc->normalized_sum_sq == nullptr)
     return set_error(PDP_E_INVALID, "accumulators.normalized_sum_sq is required by flags");
-  if (cfg->value_kind == PDP_VALUE_NONE &&
-      (cfg->flags & (PDP_ACC_SUM | PDP_ACC_NSUM | PDP_ACC_NSUM2 | PDP_SUM_PER_PARTITION)))
-    return set_error(PDP_E_INVALID, "value sums requested without a value column");
-  if (cfg->value_kind != PDP_VALUE_NONE && cfg->n_rows > 0 && value == nullptr)
-    return set_error(PDP_E_INVALID, "value column is NULL");
+  if (const int rcv = check_value_args(cfg, value); rcv != PDP_OK) return rcv;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   if (pairs_mode(cfg)) return pairs_reduce(cfg, value, ws, *acc, st);
@@ -3941,10 +3376,8 @@ int pdp_reduce_partitions(const pdp_bound_config* cfg, const void* value, void* 
     return launch_global_reduce(cfg, kp, st, value, ws, w, *acc);
   if (cfg->n_rows == 0) return PDP_OK;
   if (p.merge == PDP_MERGE_RANGES) return launch_merge(kp, p, st, ws, w, *acc);
-  if (cfg->flags & PDP_DEBUG_CORRUPT_RECORDS) {
-    rc = launch_debug_corrupt(kp, p, st, ws, w);
-    if (rc != PDP_OK) return rc;
-  }
+  rc = launch_debug_corrupt(kp, p, st, ws, w);
+  if (rc != PDP_OK) return rc;
   // PDP_MERGE_ATOMIC (never sieved: the key columns are not needed here)
   return launch_buckets(cfg->value_kind, cfg->linf == 0, kp, p, st, nullptr, nullptr, nullptr, value, *acc, ws, w);
 }

@@ -602,14 +602,14 @@ int launch_merge(const KP& kp0, const Plan& p, hipStream_t st, char* ws, const W
   KP kp = kp0;
   kp.n_buckets = p.buckets_out;
   const PairRecords rec = pair_records(ws, w, p);
-  unsigned* err = (unsigned*)(ws + w.err);
+  unsigned* err = at<unsigned>(ws, w.err);
   int rc = allow_dynamic_lds(k_range_reduce, kRangeLds);
   if (rc != PDP_OK) return rc;
-  uint4* items = (uint4*)(ws + w.rr_items);
-  unsigned* n_items = (unsigned*)(ws + w.rr_count);
+  uint4* items = at<uint4>(ws, w.rr_items);
+  unsigned* n_items = at<unsigned>(ws, w.rr_count);
   PDP_HIP_CHECK(hipMemsetAsync(n_items, 0, 4, st));
   // (the per-id fix-up writes no record segments: one segment, nothing to skip)
-  const unsigned* last_ids = p.band && !p.fix_ids ? (const unsigned*)(ws + w.sctl2) : nullptr;
+  const unsigned* last_ids = p.band && !p.fix_ids ? at<unsigned>(ws, w.sctl2) : nullptr;
   rc = launch("k_range_plan", k_range_plan, dim3((unsigned)p.n_ranges), dim3(kRangeThreads), 0, st, kp, rec.runs, items,
               n_items, last_ids, (int64_t)p.n_buckets);
   if (rc != PDP_OK) return rc;
@@ -618,27 +618,27 @@ int launch_merge(const KP& kp0, const Plan& p, hipStream_t st, char* ws, const W
                   rec, items, n_items, acc, err);
   // two-level: coarse items -> fine-range totals -> starts -> records
   // re-sorted by fine range -> fine items -> LDS sums
-  unsigned* fine_total = (unsigned*)(ws + w.fine_total);
-  unsigned* fine_cur = (unsigned*)(ws + w.fine_cur);
+  unsigned* fine_total = at<unsigned>(ws, w.fine_total);
+  unsigned* fine_cur = at<unsigned>(ws, w.fine_cur);
   PairRecords stg{};
-  stg.key = (unsigned long long*)(ws + w.stg_key);
-  stg.f0 = w.stg_f0 ? (double*)(ws + w.stg_f0) : nullptr;
-  stg.f1 = w.stg_f1 ? (double*)(ws + w.stg_f1) : nullptr;
-  stg.f2 = w.stg_f2 ? (double*)(ws + w.stg_f2) : nullptr;
+  stg.key = at<unsigned long long>(ws, w.stg_key);
+  stg.f0 = at_opt<double>(ws, w.stg_f0);
+  stg.f1 = at_opt<double>(ws, w.stg_f1);
+  stg.f2 = at_opt<double>(ws, w.stg_f2);
   PDP_HIP_CHECK(hipMemsetAsync(fine_total, 0, (uint64_t)(p.n_fine + 1) * 4, st));
-  unsigned* item_hist = (unsigned*)(ws + w.item_hist);
+  unsigned* item_hist = at<unsigned>(ws, w.item_hist);
   rc = launch("k_split_count", k_split_count, dim3((unsigned)p.n_groups), dim3(kSplitThreads), 0, st, kp, rec, items,
               n_items, fine_total, item_hist);
   if (rc != PDP_OK) return rc;
-  rc = scan_u32(fine_total, p.n_fine, (unsigned*)(ws + w.fine_chunks), st);
+  rc = scan_u32(fine_total, p.n_fine, at<unsigned>(ws, w.fine_chunks), st);
   if (rc != PDP_OK) return rc;
   PDP_HIP_CHECK(hipMemcpyAsync(fine_cur, fine_total, (uint64_t)p.n_fine * 4, hipMemcpyDeviceToDevice, st));
   const bool staged = (1 << (kp.range_bits - kRangeBits)) <= kSplitStageFan;
   rc = launch("k_split_scatter", staged ? k_split_scatter_staged : k_split_scatter, dim3((unsigned)p.n_groups),
               dim3(kSplitThreads), 0, st, kp, rec, stg, items, n_items, fine_cur, item_hist);
   if (rc != PDP_OK) return rc;
-  uint4* fitems = (uint4*)(ws + w.fine_items);
-  unsigned* n_fitems = (unsigned*)(ws + w.fine_count);
+  uint4* fitems = at<uint4>(ws, w.fine_items);
+  unsigned* n_fitems = at<unsigned>(ws, w.fine_count);
   PDP_HIP_CHECK(hipMemsetAsync(n_fitems, 0, 4, st));
   rc = launch("k_fine_plan", k_fine_plan, dim3(grid_for(p.n_fine, 1 << 20)), dim3(kBlock), 0, st, kp, fine_total,
               fitems, n_fitems);

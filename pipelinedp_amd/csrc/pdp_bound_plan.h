@@ -1,6 +1,8 @@
 // pdp_bound_plan.h -- what the bounding sources (pdp_bound*.hip) share on the
 // host: the constants of the plan and the kernels, Plan / Ws / KP /
-// PairRecords, and the entry points of the passes that have their own file.
+// PairRecords, the typed view of a workspace region (at), the planner's
+// functions (pdp_bound_planner.hip) and the entry points of the passes that
+// have their own file.
 #pragma once
 
 #include "pdp_internal.h"
@@ -81,6 +83,45 @@ constexpr unsigned kFixIdsRowCap = 4096;
 constexpr int kFixIdsThreads = 256;
 constexpr int kScanItems = 16;
 constexpr int kScanChunk = kBlock * kScanItems;
+
+// LDS of one level-1 stage, of the sieve's level-1 stage and the flush-slot
+// bits of a sieve workgroup of `threads`: sizes of StageLds / SieveShape,
+// defined beside those templates (pdp_bound.hip)
+size_t l1_stage_bytes(int key_format);
+size_t sieve_stage_bytes(int key_format, int threads);
+int sieve_slot_bits(int threads);
+// tile-local level 1 bucket counts in LDS: u32 per bucket when they fit,
+// else two u16 per word, flushed every half tile (32,768 rows: no carry) to
+// counts_tm (first half) and counts_tm2 (second half)
+inline int64_t l1_hist_bytes(int64_t n_buckets, bool u16) { return ((u16 ? 2 : 4) * n_buckets + 15) / 16 * 16; }
+constexpr int kSieveThreads2 = 512;  // the sieve's second workgroup shape (SieveShape, Plan.sieve_threads)
+// a tile's flush blocks lie back to back from tile * kSieveTileStride, its
+// band list at tile * kBandTileStride
+// (strides padded by 4 KiB measured 6 % slower at C3, profiles/r05/ab/ab1_l1_placement.txt)
+// non-temporal loads (ld_nt) of the columns level 1 streams and of the band
+// lists k_band_scan streams (C3 0.277 -> 0.255 ms); measured neutral or worse
+// and not used: k_scatter_l1_local's key loads (C4 +0.03 ms), level 2's run
+// loads and the bucket kernel's record stream (profiles/r05/ab/ab5_nt_loads.txt)
+constexpr int64_t kSieveTileStride = kTileRows;
+constexpr int64_t kBandTileStride = kTileRows;
+// tile groups per level-2 workgroup with the sieve, at most: the plan takes
+// as many as keep a workgroup's expected records (tiles x candidates per tile
+// / super-buckets) within one LDS window (kL2Target), since a second window
+// holding a few hundred records costs as much latency as a full one; and no
+// more than one level-1 slot per level-2 thread
+constexpr int kSieveL2Groups = 4;
+// the side band (Plan.band): rows with t <= pair hash < t2 = 2t leave level 1
+// as (privacy id << 32 | row) in a per-tile list, through a per-wave LDS queue
+// written out 64 entries at a time; the fix-up reads that list instead of the
+// whole privacy-id column, and only a privacy id with fewer than l0 distinct
+// pairs below t2 still needs the rescan
+constexpr int kBandQueue = 128;
+inline int64_t sieve_band_lds(int threads) { return (threads / 64) * kBandQueue * 8; }
+// LDS of a sieve workgroup: stage, bucket counts (u32, or u16 pairs), band queues
+inline int64_t sieve_lds(int key_format, int threads, int64_t n_buckets, bool u16, bool band) {
+  return ((int64_t)sieve_stage_bytes(key_format, threads) + 7) / 8 * 8 + l1_hist_bytes(n_buckets, u16) +
+         (band ? sieve_band_lds(threads) : 0);
+}
 
 struct Plan {
   int algorithm;   // PDP_ALGO_*
@@ -194,23 +235,40 @@ struct PairRecords {  // PDP_MERGE_RANGES output of the bucket kernel
   int64_t flat_base, flat_cap;
 };
 
+// The workspace region at byte offset `off` (a field of Ws) as a T*; at_opt:
+// NULL for a region the layout left out (offset 0: only the error word is there)
+template <class T> inline T* at(char* ws, uint64_t off) { return (T*)(ws + off); }
+template <class T> inline const T* at(const char* ws, uint64_t off) { return (const T*)(ws + off); }
+template <class T> inline T* at_opt(char* ws, uint64_t off) { return off ? at<T>(ws, off) : nullptr; }
+
 inline PairRecords pair_records(char* ws, const Ws& w, const Plan& p) {
   PairRecords rec{};
   if (w.runs) {
-    rec.runs = (unsigned*)(ws + w.runs);
+    rec.runs = at<unsigned>(ws, w.runs);
     rec.run_stride = p.buckets_out;
-    rec.key = (unsigned long long*)(ws + w.rec_key);
-    rec.f0 = w.rec_f0 ? (double*)(ws + w.rec_f0) : nullptr;
-    rec.f1 = w.rec_f1 ? (double*)(ws + w.rec_f1) : nullptr;
-    rec.f2 = w.rec_f2 ? (double*)(ws + w.rec_f2) : nullptr;
+    rec.key = at<unsigned long long>(ws, w.rec_key);
+    rec.f0 = at_opt<double>(ws, w.rec_f0);
+    rec.f1 = at_opt<double>(ws, w.rec_f1);
+    rec.f2 = at_opt<double>(ws, w.rec_f2);
     if (p.fix_ids) {
-      rec.flat_n = (unsigned*)(ws + w.fix_ctl) + 1;
+      rec.flat_n = at<unsigned>(ws, w.fix_ctl) + 1;
       rec.flat_cap = p.n_buckets * p.pair_slots;
       rec.flat_base = rec.flat_cap;
     }
   }
   return rec;
 }
+
+// pdp_bound_planner.hip -- what a call runs on, from its config alone: the
+// checks, the plan (infeasible: algorithm < 0), the workspace layout and the
+// kernel parameters; check_ws: validate + plan + layout + the workspace's size
+bool test_hooks_enabled();             // PIPELINEDP_AMD_TEST_HOOKS=1
+long long test_hook(const char* name);  // a hook's positive integer, else 0 (always 0 without test hooks)
+int validate(const pdp_bound_config* c);
+Plan make_plan(const pdp_bound_config* c);
+Ws layout(const pdp_bound_config* c, const Plan& p);
+KP make_kp(const pdp_bound_config* c, const Plan& p);
+int check_ws(const pdp_bound_config* cfg, const void* workspace, uint64_t workspace_bytes, Plan* p, Ws* w);
 
 // pdp_bound_merge.hip -- PDP_MERGE_RANGES: the pair records of every bucket
 // (p.buckets_out of them) summed per partition

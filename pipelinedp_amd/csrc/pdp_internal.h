@@ -509,6 +509,9 @@ __device__ __forceinline__ void add_pair_to_partition(const pdp_partition_accumu
 int64_t scan_chunk_sums_len(int64_t n);
 int scan_u32(unsigned* v, int64_t n, unsigned* chunk_sums, hipStream_t st);
 
+// compute units of the current device, 256 where the runtime cannot tell (pdp_runtime.hip)
+int64_t device_cus();
+
 // Pair-table path (pdp_pairs.hip): LinfSampler / NoOpSampler (l0 == 0),
 // SamplingPerPrivacyIdContributionBounder (max_contributions > 0) and
 // contribution_bounds_already_enforced (rows_are_units).

@@ -19,6 +19,19 @@ int set_error(int code, const char* msg) {
 
 const char* last_error() { return g_last_error.c_str(); }
 
+// compute units of the current device (cached per device)
+int64_t device_cus() {
+  static int cached[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cached[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cached[dev] = n;
+  }
+  return cached[dev];
+}
+
 // profiler: (name, start, stop) event triples, resolved by pdp_profiler_report
 namespace {
 struct ProfRecord {
