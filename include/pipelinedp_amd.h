@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 19
+#define PDP_ABI_VERSION 20
 
 /* error codes */
 #define PDP_OK 0
@@ -370,6 +370,74 @@ int pdp_vector_sum_metrics(const double* vector_acc, int32_t vector_size, int32_
                            const pdp_noise_params* noise, const int64_t* index, int64_t n_kept,
                            const int64_t* n_kept_dev, int64_t partition_offset, double* out, uint64_t seed,
                            void* stream);
+
+/* PERCENTILE (QuantileCombiner, combiners.py:590-669): one quantile tree per
+ * partition over [min_value, max_value], height 4, branching factor 16.  The
+ * reference delegates the tree to PyDP's QuantileTree; the algorithm these
+ * entry points run is restated in DESIGN.md section 3 ("PERCENTILE") and was
+ * not compared against PyDP output.  Node 0 is the root (never counted), the
+ * children of node i are 16 i + 1 ... 16 i + 16, the 65,536 leaves are the
+ * nodes from 4,369 on, and a partition has 69,904 counted nodes.
+ *
+ * A value's leaf is min(65535, floor((clamp(v) - min_value) / (max_value -
+ * min_value) * 65536)) in fp64, clamp(v) to [min_value, max_value]; a NaN
+ * value takes no part.  A node's raw count is the number of kept rows whose
+ * leaf lies in its leaf range, so the tree of a partition is held as the
+ * ascending array of its kept rows' 16-bit leaf codes. */
+#define PDP_MAX_QUANTILES 64
+
+/* Philox stream slot of the quantile trees' noise ("QNTL"): none of the slots
+ * listed at PDP_VECTOR_SUM_SLOT, nor that one. */
+#define PDP_QUANTILE_SLOT 0x514E544C
+
+/* Bytes of device workspace for pdp_bound_contributions followed by
+ * pdp_reduce_quantile_leaves: the pair table's workspace, the kept-row marks
+ * and per-partition counts, and the leaf sort's key columns (16 B per row). */
+int pdp_quantile_workspace_bytes(const pdp_bound_config* cfg, uint64_t* bytes);
+
+/* QuantileCombiner.create_accumulator per kept pair, merged per partition
+ * (combiners.py:608-620), in columnar form: leaves[offsets[p] .. offsets[p + 1])
+ * = the ascending leaf codes of the rows of partition p the bounder keeps,
+ * exactly the rows pdp_reduce_vector_sum would sum, less those whose value is
+ * NaN.  value: n_rows doubles (PDP_VALUE_F64) or int64 (PDP_VALUE_I64).
+ * leaves: device uint16[n_rows] (only the first offsets[n_partitions] are
+ * written); offsets: device uint32[n_partitions + 1].  Both are overwritten.
+ * The preconditions are pdp_reduce_vector_sum's: it must follow
+ * pdp_bound_contributions on the same workspace (of at least
+ * pdp_quantile_workspace_bytes) and stream, with the same cfg, key columns and
+ * pk_allowed, and cfg must resolve to PDP_ALGO_PAIR_TABLE (any other plan:
+ * PDP_E_UNSUPPORTED); out-of-range keys set bit 0 of the error word and are
+ * skipped.  n_rows < 2^31, n_partitions < 2^31 - 1.  The kept rows are marked
+ * and counted per partition as for VECTOR_SUM, and the (leaf, partition) keys
+ * are ordered by the stable tile sort, 8 bits a pass, leaf digits first: two
+ * runs give the same bytes. */
+int pdp_reduce_quantile_leaves(const pdp_bound_config* cfg, const int64_t* privacy_id, const int64_t* partition_key,
+                               const uint8_t* pk_allowed, const void* value, int32_t value_kind, double min_value,
+                               double max_value, void* workspace, uint64_t workspace_bytes, uint16_t* leaves,
+                               uint32_t* offsets, void* stream);
+
+/* QuantileCombiner.compute_metrics (combiners.py:622-633 ->
+ * QuantileTree.compute_quantiles) for the kept partitions: for each i < n_kept
+ * with p = index[i] and each j < n_ranks,
+ *   out[i * n_ranks + j] = the value at rank ranks[j] of partition p's tree.
+ * ranks: HOST array of n_ranks values in [0, 1], 1 <= n_ranks <=
+ * PDP_MAX_QUANTILES.  A node's noised count is max(0, noise(raw count)), the
+ * secure mechanism `noise` (host pointer; granularity 0 = no noise) on the
+ * Philox stream (seed, (partition_offset + p) * 69904 + node - 1,
+ * PDP_QUANTILE_SLOT): one value per node, whichever rank asks for it.  The
+ * walk from the root takes, four times, the first child whose share of the
+ * children's noised total reaches the rank (less 1e-6), rescales the rank into
+ * that child and narrows [min_value, max_value] to its sixteenth; it stops
+ * early where the children's total is not positive, and returns
+ * (1 - rank) * a + rank * b on the range [a, b] it reached.  A partition
+ * without rows walks on noise alone (no noise: (1 - rank) * min_value + rank *
+ * max_value).  One wave per partition, 16 lanes (children) per rank, four
+ * ranks a round; every fp64 operation is rounded on its own (no contraction),
+ * in the order DESIGN.md states.  n_kept_dev as in pdp_noise_metrics. */
+int pdp_quantile_metrics(const uint16_t* leaves, const uint32_t* offsets, int64_t n_partitions, double min_value,
+                         double max_value, const double* ranks, int32_t n_ranks, const pdp_noise_params* noise,
+                         const int64_t* index, int64_t n_kept, const int64_t* n_kept_dev, int64_t partition_offset,
+                         double* out, uint64_t seed, void* stream);
 
 /* DPEngine.add_dp_noise (dp_engine.py:551-607): out[i] = the secure
  * mechanism `noise` applied to (double)values[i], the `lambda value:

@@ -246,6 +246,8 @@ class AggregateParams:
             if bad:
                 raise ValueError(f"AggregateParams: for metrics {bad} bounds per partition are "
                                  f"required (e.g. min_value,max_value).")
+        if any(m.is_percentile for m in metrics) and value_bound and not self.min_value < self.max_value:
+            raise ValueError("AggregateParams: PERCENTILE needs min_value < max_value (the quantile tree's range)")
         if self.contribution_bounds_already_enforced and Metrics.PRIVACY_ID_COUNT in metrics:
             raise ValueError("AggregateParams: Cannot calculate PRIVACY_ID_COUNT when "
                              "contribution_bounds_already_enforced is set to True.")

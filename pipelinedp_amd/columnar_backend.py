@@ -35,6 +35,7 @@ from pipelinedp_amd import dp_computations as dpc
 from pipelinedp_amd import parallel
 from pipelinedp_amd import partition_selection as ps
 from pipelinedp_amd import pipeline_backend
+from pipelinedp_amd import quantile_tree
 
 # stage names DPEngine / the bounders use (reference file:line)
 ST_EXTRACT = "Extract (privacy_id, partition_key, value))"          # dp_engine.py:415
@@ -329,11 +330,13 @@ class MetricsProgram:
         self.int_bounds = True
         self.needs_values = False
         self.threshold_combiner = None
-        self.vector = None       # VectorSumCombiner: VectorProgram (its field comes last)
+        self.vector = None       # VectorSumCombiner: VectorProgram (its field follows the scalar ones)
+        self.quantile = None     # QuantileCombiner: QuantileProgram (its fields come last)
 
     @property
     def all_fields(self):
-        return self.fields + (["vector_sum"] if self.vector is not None else [])
+        return (self.fields + (["vector_sum"] if self.vector is not None else []) +
+                (self.quantile.names if self.quantile is not None else []))
 
 
 class VectorProgram:
@@ -344,6 +347,17 @@ class VectorProgram:
         self.norm_kind = norm_kind   # N.NORM_*
         self.max_norm = float(max_norm)
         self.noise = noise           # dpc.NoiseParams, per coordinate
+
+
+class QuantileProgram:
+    """pdp_reduce_quantile_leaves / pdp_quantile_metrics arguments of a QuantileCombiner."""
+
+    def __init__(self, min_value, max_value, ranks, names, noise):
+        self.min_value = float(min_value)
+        self.max_value = float(max_value)
+        self.ranks = [float(r) for r in ranks]
+        self.names = list(names)     # one result column per percentile
+        self.noise = noise           # dpc.NoiseParams of a node count
 
 
 _NORM_CODES = {"linf": N.NORM_LINF, "l1": N.NORM_L1, "l2": N.NORM_L2}
@@ -438,11 +452,28 @@ def build_metrics_program(compound, params) -> MetricsProgram:
                                      c._params.delta / p.vector_size, p.max_partitions_contributed,
                                      p.max_contributions_per_partition)
             prog.vector = VectorProgram(p.vector_size, _NORM_CODES[norm], p.vector_max_norm, noise)
+        elif name == "QuantileCombiner":
+            p = c._params.aggregate_params
+            # from the configuration alone (_params, _percentiles): the reference's combiner has no more
+            ranks = [pct / 100 for pct in c._percentiles]
+            if not 1 <= len(ranks) <= N.MAX_QUANTILES:
+                raise NotImplementedError(f"{len(ranks)} percentiles in one aggregation: the supported range is "
+                                          f"[1, {N.MAX_QUANTILES}]")
+            if any(not 0.0 <= r <= 1.0 for r in ranks):
+                raise ValueError(f"percentiles must lie in [0, 100], got {list(c._percentiles)}")
+            # one mechanism for every node count: L0 = l0 * tree height, Linf = linf
+            noise = dpc.noise_params(_to_local_noise_kind(p.noise_kind), c._params.eps, c._params.delta,
+                                     p.max_partitions_contributed * quantile_tree.HEIGHT,
+                                     p.max_contributions_per_partition)
+            prog.quantile = QuantileProgram(p.min_value, p.max_value, ranks, c.metrics_names(), noise)
         else:
             raise NotImplementedError(f"{name} is not supported by ColumnarBackend "
-                                      "(hot path: Count/Sum/Mean/Variance/PrivacyIdCount/VectorSum)")
+                                      "(hot path: Count/Sum/Mean/Variance/PrivacyIdCount/VectorSum/Quantile)")
     if prog.vector is not None and prog.needs_values:
         raise NotImplementedError("VECTOR_SUM cannot be combined with scalar value metrics")
+    if prog.quantile is not None and (prog.needs_values or prog.vector is not None):
+        raise NotImplementedError("PERCENTILE together with SUM, MEAN, VARIANCE or VECTOR_SUM is not "
+                                  "implemented: the quantile trees run with COUNT and PRIVACY_ID_COUNT only")
     return prog
 
 
@@ -659,7 +690,8 @@ class AggregateRun:
             rows = [self.plan.extract_fn(r) for r in src]
             pid_raw = [r[0] for r in rows]
             pk_raw = [r[1] for r in rows]
-            val_raw = [r[2] for r in rows] if self.prog.needs_values or self.prog.vector is not None else None
+            wants = self.prog.needs_values or self.prog.vector is not None or self.prog.quantile is not None
+            val_raw = [r[2] for r in rows] if wants else None
             n_pid = n_pk = None
             pk_decode = None
         units = self.plan.bounder == "already_enforced"  # no privacy ids on this path
@@ -691,6 +723,13 @@ class AggregateRun:
             if val_raw is None:
                 raise ValueError("the value extractor must return the vector column for VECTOR_SUM")
             val_t = _vector_tensor(val_raw, self.prog.vector.size, device)
+        elif self.prog.quantile is not None:
+            if parallel.world_info()[0] > 1:
+                raise NotImplementedError("PERCENTILE runs on one GPU: the exchange of the partitions' quantile "
+                                          "trees across ranks is not implemented")
+            if val_raw is None:
+                raise ValueError("the value extractor must return a value column for PERCENTILE")
+            val_t = _value_tensor(val_raw, device)  # bounding sees no value column: value_kind stays NONE
         elif self.prog.needs_values:
             if val_raw is None:
                 raise ValueError("the value extractor must return a value column for SUM/MEAN/VARIANCE")
@@ -745,6 +784,7 @@ class AggregateRun:
         seed_bound, _, _ = self._seeds
         n_pid = 1 if pid_enc is None else pid_enc.n
         self._vector_acc = None
+        self._quantile_trees = None
         if self.prog.vector is not None:
             # the values never pass through the pair table: bounding sees no value column
             if self.backend._workspace is None:
@@ -752,6 +792,17 @@ class AggregateRun:
             acc, self._vector_acc = X.reduce_vector_sum(
                 pid_t, pk_t, val_t, n_privacy_ids=n_pid, n_partitions=P, bounding=spec, seed=seed_bound,
                 allowed=allowed, row_offset=row_offset, workspace=self.backend._workspace, check_keys="defer")
+            self.backend.last_plan_info = X.bound_plan(pk_t.numel(), n_pid, P, spec, algorithm=N.ALGO_PAIR_TABLE)
+            self.backend.last_bounding = spec
+        elif self.prog.quantile is not None:
+            # as VECTOR_SUM: the pair table says which rows are kept, their values go to the leaf sort
+            if self.backend._workspace is None:
+                self.backend._workspace = X.BoundWorkspace()
+            q = self.prog.quantile
+            acc, *self._quantile_trees = X.reduce_quantile_leaves(
+                pid_t, pk_t, val_t, n_privacy_ids=n_pid, n_partitions=P, bounding=spec, min_value=q.min_value,
+                max_value=q.max_value, seed=seed_bound, allowed=allowed, row_offset=row_offset,
+                workspace=self.backend._workspace, check_keys="defer")
             self.backend.last_plan_info = X.bound_plan(pk_t.numel(), n_pid, P, spec, algorithm=N.ALGO_PAIR_TABLE)
             self.backend.last_bounding = spec
         elif pk_t.numel() == 0:
@@ -818,6 +869,13 @@ class AggregateRun:
             vout = X.vector_sum_metrics(self._vector_acc, index, norm_kind=v.norm_kind, max_norm=v.max_norm,
                                         noise=v.noise, seed=seed_noise, n_kept_dev=n_kept_dev,
                                         partition_offset=first)
+        qout = None
+        if self.prog.quantile is not None:  # QuantileCombiner.compute_metrics of the kept partitions
+            q = self.prog.quantile
+            leaves, offsets = self._quantile_trees
+            qout = X.quantile_metrics(leaves, offsets, index, min_value=q.min_value, max_value=q.max_value,
+                                      ranks=q.ranks, noise=q.noise, seed=seed_noise, n_kept_dev=n_kept_dev,
+                                      partition_offset=first)
         # the kept count and the kept columns in one round trip (one stream sync)
         idx, vals, n_kept = X.kept_to_host_guess(index, out, n_kept_dev, keys_only=self.plan.keys_only,
                                                  key=(int(index.shape[0]), len(self.prog.fields),
@@ -835,6 +893,10 @@ class AggregateRun:
         cols = {f: np.ascontiguousarray(vals[c][keep]) for c, f in enumerate(self.prog.fields)}
         if vout is not None:  # [kept, vector_size]: one np.ndarray per partition
             cols["vector_sum"] = np.ascontiguousarray(vout[:n_kept].cpu().numpy()[keep])
+        if qout is not None:  # [kept, percentiles]: one column per percentile
+            qhost = qout[:n_kept].cpu().numpy()[keep]
+            for j, f in enumerate(self.prog.quantile.names):
+                cols[f] = np.ascontiguousarray(qhost[:, j])
         return C.AggregateResult(pk_enc.keys_of(first + idx[keep]), cols, nt)
 
     def raw_accumulators(self):
@@ -843,6 +905,10 @@ class AggregateRun:
         self._raise_key_errors()
         public = allowed.cpu().numpy().astype(bool) if allowed is not None else None
         vhost = None if self._vector_acc is None else self._vector_acc.cpu().numpy()
+        qleaves = qoff = None
+        if self._quantile_trees is not None:
+            qleaves = self._quantile_trees[0].cpu().numpy().view(np.uint16)
+            qoff = self._quantile_trees[1].cpu().numpy().view(np.uint32)
         out = {}
         for p in range(pk_enc.n):
             rc = int(host["privacy_id_count"][p])
@@ -867,6 +933,8 @@ class AggregateRun:
                                      float(host["normalized_sum_sq"][p])))
                 elif name == "VectorSumCombiner":
                     children.append(vhost[p].copy())
+                elif name == "QuantileCombiner":
+                    children.append(qleaves[qoff[p]:qoff[p + 1]].copy())
             row_count = rc + (1 if public is not None else 0)  # empty public accumulator
             out[pk_enc.key_of(p)] = (row_count, tuple(children))
         return out

@@ -7,8 +7,11 @@ ColumnarBackend these methods are never called per row: the backend reads
 the combiner's configuration (bounds, mechanism specs, metric names) and runs
 the same arithmetic in the HIP kernels (csrc/pdp_bound.hip, pdp_select.hip).
 VectorSumCombiner's accumulator and metrics run in pdp_pairs.hip /
-pdp_select.hip (pdp_reduce_vector_sum, pdp_vector_sum_metrics).  Quantile and
-custom combiners are outside the hot path.
+pdp_select.hip (pdp_reduce_vector_sum, pdp_vector_sum_metrics), and
+QuantileCombiner's quantile trees in pdp_quantiles.hip
+(pdp_reduce_quantile_leaves, pdp_quantile_metrics); its row-wise methods run
+the same tree in NumPy (quantile_tree.py).  Custom combiners are outside the
+hot path.
 """
 import abc
 import collections
@@ -21,6 +24,7 @@ from pipelinedp_amd import aggregate_params as agg
 from pipelinedp_amd import budget_accounting
 from pipelinedp_amd import dp_computations as dpc
 from pipelinedp_amd import partition_selection
+from pipelinedp_amd import quantile_tree
 
 
 class Combiner(abc.ABC):
@@ -414,6 +418,70 @@ class VectorSumCombiner(Combiner):
         return self._params.mechanism_spec
 
 
+class QuantileCombiner(Combiner):
+    """Percentiles from one DP quantile tree per partition (reference :590-669,
+    whose tree is PyDP's QuantileTree; here quantile_tree.py, restated in
+    DESIGN.md §3 "PERCENTILE").  Accumulator: the uint16 leaf codes of the
+    values over [min_value, max_value] (NaN values are left out).  One
+    mechanism noises every node count, with L0 sensitivity
+    max_partitions_contributed * tree height and Linf sensitivity
+    max_contributions_per_partition; all percentiles read the same noisy tree."""
+
+    def __init__(self, params: CombinerParams, percentiles_to_compute: List[float]):
+        self._params = params
+        self._percentiles = list(percentiles_to_compute)
+
+    @property
+    def params(self) -> CombinerParams:
+        return self._params
+
+    @property
+    def percentiles(self) -> List[float]:
+        return list(self._percentiles)
+
+    @property
+    def ranks(self) -> List[float]:
+        return [p / 100 for p in self._percentiles]
+
+    def _range(self):
+        p = self._params.aggregate_params
+        return p.min_value, p.max_value
+
+    def noise_params(self) -> dpc.NoiseParams:
+        """The secure sampler of a node count: L1 = L0 * Linf (Laplace) or
+        L2 = sqrt(L0) * Linf (Gaussian) with L0 = l0 * height, Linf = linf."""
+        p = self._params.aggregate_params
+        return dpc.noise_params(p.noise_kind, self._params.eps, self._params.delta,
+                                p.max_partitions_contributed * quantile_tree.HEIGHT,
+                                p.max_contributions_per_partition)
+
+    def create_accumulator(self, values) -> np.ndarray:
+        return quantile_tree.leaf_codes(values, *self._range())
+
+    def merge_accumulators(self, leaves1: np.ndarray, leaves2: np.ndarray) -> np.ndarray:
+        return np.concatenate([leaves1, leaves2])
+
+    def compute_metrics(self, leaves: np.ndarray) -> dict:
+        noise, sampler = self.noise_params(), dpc.secure_sampler()
+        values = quantile_tree.compute_quantiles(leaves, *self._range(), self.ranks,
+                                                 lambda node, raw: sampler.add_noise(noise, raw))
+        return dict(zip(self.metrics_names(), values))
+
+    def metrics_names(self) -> List[str]:
+        names = []
+        for p in self._percentiles:
+            whole = int(round(p))
+            names.append(f"percentile_{whole}" if whole == p else "percentile_" + str(p).replace(".", "_"))
+        return names
+
+    def explain_computation(self):
+        return lambda: (f"Computed percentiles {self._percentiles} with "
+                        f"(eps={self._params.eps} delta={self._params.delta})")
+
+    def mechanism_spec(self):
+        return self._params.mechanism_spec
+
+
 def variance_noise_scales(dp_params: dpc.ScalarNoiseParams):
     """Noise scales of compute_dp_var's three mechanisms (reference
     dp_computations.py:306-365): count, normalised sum, normalised sum of
@@ -575,6 +643,38 @@ def create_compound_combiner(aggregate_params: agg.AggregateParams,
     if any(m.is_percentile for m in metrics):
         raise NotImplementedError("PERCENTILE (PyDP quantile trees) is not on the pipelinedp_amd hot path")
     return CompoundCombiner(combiners, return_named_tuple=True)
+
+
+def create_compound_combiner_with_percentiles(aggregate_params: agg.AggregateParams,
+                                              budget_accountant) -> CompoundCombiner:
+    """create_compound_combiner for params whose metrics include PERCENTILE.
+
+    There are two factories because create_compound_combiner is pinned as it
+    is: it builds every other combiner in the reference's order and goes on
+    refusing percentiles (tests/test_vector_sum_host.py asserts that).  This one
+    calls it on a copy of the params without the percentile metrics, then
+    requests ONE budget for all percentiles, last, which is the reference's
+    order (:909-920), and appends the QuantileCombiner.  DPEngine uses it
+    whenever a metric is a percentile.
+
+    PERCENTILE runs with COUNT and / or PRIVACY_ID_COUNT or alone; with SUM,
+    MEAN, VARIANCE or VECTOR_SUM it raises NotImplementedError."""
+    percentiles = [m.parameter for m in aggregate_params.metrics if m.is_percentile]
+    if not percentiles:
+        raise ValueError("create_compound_combiner_with_percentiles: no PERCENTILE metric in the params")
+    others = [m for m in aggregate_params.metrics if not m.is_percentile]
+    refused = [m for m in others if m in (agg.Metrics.SUM, agg.Metrics.MEAN, agg.Metrics.VARIANCE,
+                                          agg.Metrics.VECTOR_SUM)]
+    if refused:
+        raise NotImplementedError(f"PERCENTILE together with {refused} is not implemented: the quantile "
+                                  f"trees run with COUNT and PRIVACY_ID_COUNT only")
+    without = copy.copy(aggregate_params)
+    without.metrics = others
+    compound = create_compound_combiner(without, budget_accountant)
+    budget = budget_accountant.request_budget(aggregate_params.noise_kind.convert_to_mechanism_type(),
+                                              weight=aggregate_params.budget_weight)
+    quantiles = QuantileCombiner(CombinerParams(budget, aggregate_params), percentiles)
+    return CompoundCombiner(compound.combiners + [quantiles], return_named_tuple=True)
 
 
 def create_compound_combiner_with_custom_combiners(aggregate_params, budget_accountant,

@@ -529,6 +529,20 @@ int pairs_bound(const pdp_bound_config* c, const int64_t* pid, const int64_t* pk
                 const uint8_t* allowed, char* ws, hipStream_t st);
 int pairs_reduce(const pdp_bound_config* c, const void* value, char* ws, const pdp_partition_accumulators& acc,
                  hipStream_t st);
+// The rows the pair table kept (VECTOR_SUM sums them, PERCENTILE sorts their
+// leaf codes): pairs_mark_kept_rows after pairs_bound on a workspace of at
+// least pairs_vector_workspace_bytes(c, 0) bytes.
+constexpr unsigned kPairsNotKept = ~0u;
+struct PairsKeptRows {
+  unsigned* mark;  // [n_rows]: the partition of a kept row, else kPairsNotKept
+  unsigned* off;   // [n_partitions + 1]: exclusive scan of the kept rows per partition
+};
+uint64_t pairs_vector_workspace_bytes(const pdp_bound_config* c, int vector_size);
+int pairs_mark_kept_rows(const pdp_bound_config* c, const int64_t* pid, const int64_t* pk, const uint8_t* allowed,
+                         const double* drop_nan, char* ws, PairsKeptRows* kr, hipStream_t st);
+
+// host-side validation of one mechanism's parameters (pdp_select.hip)
+int check_noise(const pdp_noise_params* np);
 
 }  // namespace pdp
 

@@ -709,7 +709,7 @@ struct RunUnits {
 //                 only writer
 // No atomic touches a double: a hot partition is split over the tiles' waves.
 constexpr unsigned kVsTile = 1024;
-constexpr unsigned kVsNone = ~0u;
+constexpr unsigned kVsNone = kPairsNotKept;
 
 struct VWs {
   uint64_t mark, rows, pcnt, pcur, chunks, partial, total;
@@ -775,14 +775,17 @@ __device__ __forceinline__ bool vs_row_kept(const PT& t, const VsTab& tb, const 
   return y <= tb.pair_pool[(uint64_t)tb.pair_off[slot] + t.linf - 1];
 }
 
+// drop_nan (nullable, PERCENTILE): a kept row whose fp64 value is NaN is marked as not kept
 __global__ void __launch_bounds__(kBlock) k_vs_mark(PT t, VsTab tb, const int64_t* __restrict__ pid,
                                                     const int64_t* __restrict__ pk,
-                                                    const uint8_t* __restrict__ allowed, unsigned* mark,
+                                                    const uint8_t* __restrict__ allowed,
+                                                    const double* __restrict__ drop_nan, unsigned* mark,
                                                     unsigned* pcnt, unsigned* err) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += stride) {
     int64_t k;
-    const bool kept = vs_row_kept(t, tb, pid, pk, allowed, i, &k, err);
+    bool kept = vs_row_kept(t, tb, pid, pk, allowed, i, &k, err);
+    if (kept && drop_nan != nullptr) kept = drop_nan[i] == drop_nan[i];
     mark[i] = kept ? (unsigned)k : kVsNone;
     if (kept) atomicAdd(pcnt + k, 1u);
   }
@@ -927,19 +930,21 @@ uint64_t pairs_vector_workspace_bytes(const pdp_bound_config* c, int vector_size
   return vlayout(c, vector_size).total;
 }
 
-int pairs_vector_sum(const pdp_bound_config* c, const int64_t* pid, const int64_t* pk, const uint8_t* allowed,
-                     const double* vectors, int d, char* ws, double* vector_acc, hipStream_t st) {
+// The kept rows of the table pairs_bound left in `ws`, marked and counted:
+// kr->mark[i] = partition of kept row i (kPairsNotKept otherwise), kr->off =
+// the partitions' first positions in a list of the kept rows sorted by
+// partition (off[P] = their number).  drop_nan: see k_vs_mark.
+int pairs_mark_kept_rows(const pdp_bound_config* c, const int64_t* pid, const int64_t* pk, const uint8_t* allowed,
+                         const double* drop_nan, char* ws, PairsKeptRows* kr, hipStream_t st) {
   const PWs w = playout(c);
-  const VWs v = vlayout(c, d);
+  const VWs v = vlayout(c, 0);  // the regions before `partial` do not depend on the vector size
   const PT t = make_pt(c);
   const int64_t n = c->n_rows, P = c->n_partitions;
-  if (n == 0) return PDP_OK;
   unsigned* pcnt = (unsigned*)(ws + v.pcnt);
-  unsigned* pcur = (unsigned*)(ws + v.pcur);
-  unsigned* mark = (unsigned*)(ws + v.mark);
-  unsigned* rows = (unsigned*)(ws + v.rows);
+  kr->mark = (unsigned*)(ws + v.mark);
+  kr->off = pcnt;
   PDP_HIP_CHECK(hipMemsetAsync(pcnt, 0, ((uint64_t)P + 1) * 4, st));
-  PDP_HIP_CHECK(hipMemsetAsync(pcur, 0, (uint64_t)P * 4, st));
+  if (n == 0) return PDP_OK;
   VsTab tb{};
   if (!c->rows_are_units) {
     const bool per_pid = t.maxc > 0 || t.l0 > 0;
@@ -952,12 +957,24 @@ int pairs_vector_sum(const pdp_bound_config* c, const int64_t* pid, const int64_
     tb.pair_pool = t.linf > 0 ? (const unsigned long long*)(ws + w.pair_pool) : nullptr;
     tb.keep = t.l0 > 0 ? (const uint8_t*)(ws + w.pkeep) : nullptr;
   }
-  const unsigned g = grid_for(n);
-  if (int rc = launch("k_vs_mark", k_vs_mark, dim3(g), dim3(kBlock), 0, st, t, tb, c->rows_are_units ? nullptr : pid,
-                      pk, allowed, mark, pcnt, (unsigned*)(ws + w.err)); rc != PDP_OK) return rc;
-  const int rc = scan_u32(pcnt, P, (unsigned*)(ws + v.chunks), st);
-  if (rc != PDP_OK) return rc;
-  if (int rc = launch("k_vs_scatter", k_vs_scatter, dim3(g), dim3(kBlock), 0, st, n, P, mark, pcnt, pcur,
+  if (int rc = launch("k_vs_mark", k_vs_mark, dim3(grid_for(n)), dim3(kBlock), 0, st, t, tb,
+                      c->rows_are_units ? nullptr : pid, pk, allowed, drop_nan, kr->mark, pcnt,
+                      (unsigned*)(ws + w.err)); rc != PDP_OK) return rc;
+  return scan_u32(pcnt, P, (unsigned*)(ws + v.chunks), st);
+}
+
+int pairs_vector_sum(const pdp_bound_config* c, const int64_t* pid, const int64_t* pk, const uint8_t* allowed,
+                     const double* vectors, int d, char* ws, double* vector_acc, hipStream_t st) {
+  const VWs v = vlayout(c, d);
+  const int64_t n = c->n_rows, P = c->n_partitions;
+  if (n == 0) return PDP_OK;
+  PairsKeptRows kr;
+  if (int rc = pairs_mark_kept_rows(c, pid, pk, allowed, nullptr, ws, &kr, st); rc != PDP_OK) return rc;
+  unsigned* pcnt = kr.off;
+  unsigned* pcur = (unsigned*)(ws + v.pcur);
+  unsigned* rows = (unsigned*)(ws + v.rows);
+  PDP_HIP_CHECK(hipMemsetAsync(pcur, 0, (uint64_t)P * 4, st));
+  if (int rc = launch("k_vs_scatter", k_vs_scatter, dim3(grid_for(n)), dim3(kBlock), 0, st, n, P, kr.mark, pcnt, pcur,
                       rows); rc != PDP_OK) return rc;
   double* partial = (double*)(ws + v.partial);
   // 16 B per lane where every row and the accumulator rows are 16-byte aligned

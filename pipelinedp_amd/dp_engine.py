@@ -264,6 +264,8 @@ class DPEngine:
                                     "Drop partitions under threshold")
 
     def _create_compound_combiner(self, params):
+        if any(m.is_percentile for m in params.metrics):
+            return combiners.create_compound_combiner_with_percentiles(params, self._budget_accountant)
         return combiners.create_compound_combiner(params, self._budget_accountant)
 
     def _create_contribution_bounder(self, params, expects_per_partition_sampling: bool):

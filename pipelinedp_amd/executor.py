@@ -718,6 +718,101 @@ def vector_sum_metrics(vector_acc, index, *, norm_kind: int, max_norm: float, no
     return out
 
 
+def reduce_quantile_leaves(pid, pk, values, *, n_privacy_ids: int, n_partitions: int, bounding: BoundingSpec,
+                           min_value: float, max_value: float, seed: int, row_offset: int = 0, allowed=None,
+                           acc=None, workspace: Optional[BoundWorkspace] = None, stream=None, check_keys=True,
+                           algorithm: int = N.ALGO_PAIR_TABLE):
+    """PERCENTILE's bounding + reduction of one shard: bounds the contributions
+    on the pair table (`pdp_bound_contributions`; `bounding`'s l0 / linf /
+    max_contributions / rows_are_units, no value column), ADDS the row /
+    privacy-id counts to `acc` (`pdp_reduce_partitions`) and builds every
+    partition's quantile tree from the kept rows' values
+    (`pdp_reduce_quantile_leaves`).
+
+    values: float64 or int64 device tensor [n].  Returns (acc, leaves,
+    offsets): leaves int16 [n] (uint16 bits), offsets int32 [n_partitions + 1] (uint32 bits);
+    partition p's ascending leaf codes are leaves[offsets[p]:offsets[p + 1]]."""
+    torch = _torch()
+    lib = N.lib()
+    device = pk.device
+    n = int(pk.shape[0])
+    if pid is None and not bounding.rows_are_units:
+        raise ValueError("privacy_id is required unless contribution bounds are already enforced")
+    if pid is not None:
+        _check_col(pid, "privacy_id", (torch.int64,), n, device)
+    _check_col(pk, "partition_key", (torch.int64,), n, device)
+    _check_col(values, "values", (torch.float64, torch.int64), n, device)
+    if allowed is not None:
+        _check_col(allowed, "pk_allowed", (torch.uint8,), int(n_partitions), device)
+    counts = dataclasses.replace(bounding, value_kind=N.VALUE_NONE, flags=0)
+    cfg = bound_config(n, n_privacy_ids, n_partitions, counts, seed, row_offset, algorithm)
+    nbytes = ctypes.c_uint64(0)
+    N.check(lib.pdp_quantile_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes)), "pdp_quantile_workspace_bytes")
+    wsobj = workspace or BoundWorkspace()
+    ws = wsobj.get(nbytes.value, device)
+    wsobj.last_cfg = cfg
+    if acc is None:
+        acc = new_accumulators(n_partitions, counts, device)
+    leaves = torch.empty(max(n, 1), dtype=torch.int16, device=device)
+    offsets = torch.empty(int(n_partitions) + 1, dtype=torch.int32, device=device)
+    sobj = stream if stream is not None else torch.cuda.current_stream(device)
+    st = int(sobj.cuda_stream)
+    N.check(lib.pdp_bound_contributions(ctypes.byref(cfg), _ptr(pid), _ptr(pk), None, _ptr(allowed), _ptr(ws),
+                                        ws.numel(), st), "pdp_bound_contributions")
+    N.check(lib.pdp_reduce_partitions(ctypes.byref(cfg), None, _ptr(ws), ws.numel(),
+                                      ctypes.byref(_acc_struct(acc)), st), "pdp_reduce_partitions")
+    vk = N.VALUE_I64 if values.dtype == torch.int64 else N.VALUE_F64
+    N.check(lib.pdp_reduce_quantile_leaves(ctypes.byref(cfg), _ptr(pid), _ptr(pk), _ptr(allowed), _ptr(values), vk,
+                                           float(min_value), float(max_value), _ptr(ws), ws.numel(), _ptr(leaves),
+                                           _ptr(offsets), st), "pdp_reduce_quantile_leaves")
+    if check_keys == "defer" and workspace is not None:
+        wsobj.defer_error_check(ws, sobj, n_privacy_ids, n_partitions)
+    elif check_keys:
+        flags = ctypes.c_uint32(0)
+        N.check(lib.pdp_bound_error_flags(_ptr(ws), ctypes.byref(flags), st), "pdp_bound_error_flags")
+        _raise_error_flags(flags.value, n_privacy_ids, n_partitions)
+    return acc, leaves, offsets
+
+
+def quantile_metrics(leaves, offsets, index, *, min_value: float, max_value: float, ranks: Sequence[float],
+                     noise: NoiseParams, seed: int, n_kept: Optional[int] = None, n_kept_dev=None,
+                     partition_offset: int = 0, out=None, stream=None):
+    """QuantileCombiner.compute_metrics for the kept partitions
+    (`pdp_quantile_metrics`): entry [i, j] of the result is the value at rank
+    ranks[j] (in [0, 1]) of the quantile tree of partition index[i], every node
+    count noised once by the secure mechanism `noise` (NO_NOISE: the exact
+    tree).  leaves / offsets: from reduce_quantile_leaves.  n_kept defaults to
+    len(index); n_kept_dev (device int64[1]) bounds it on the device.  Returns
+    a float64 device tensor [n_kept, len(ranks)]."""
+    torch = _torch()
+    lib = N.lib()
+    device = offsets.device
+    P = int(offsets.shape[0]) - 1
+    _check_col(offsets, "offsets", (torch.int32,), P + 1, device)
+    _check_col(leaves, "leaves", (torch.int16,), int(leaves.shape[0]), device)
+    cap = int(index.shape[0])
+    _check_col(index, "index", (torch.int64,), cap, device)
+    n_kept = cap if n_kept is None else int(n_kept)
+    if n_kept < 0 or n_kept > cap:
+        raise ValueError(f"n_kept={n_kept} is outside [0, {cap}]")
+    if n_kept_dev is not None:
+        _check_col(n_kept_dev, "n_kept_dev", (torch.int64,), 1, device)
+    ranks = [float(r) for r in ranks]
+    if not 1 <= len(ranks) <= N.MAX_QUANTILES:
+        raise NotImplementedError(f"{len(ranks)} percentiles in one aggregation: the supported range is "
+                                  f"[1, {N.MAX_QUANTILES}]")
+    if out is None:
+        out = torch.empty((n_kept, len(ranks)), dtype=torch.float64, device=device)
+    _check_matrix(out, "out", n_kept, len(ranks), device)
+    c_ranks = (ctypes.c_double * len(ranks))(*ranks)
+    c_noise = (noise or NO_NOISE).to_c()
+    N.check(lib.pdp_quantile_metrics(_ptr(leaves), _ptr(offsets), P, float(min_value), float(max_value), c_ranks,
+                                     len(ranks), ctypes.byref(c_noise), _ptr(index), n_kept, _ptr(n_kept_dev),
+                                     int(partition_offset), _ptr(out), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     _stream(stream)), "pdp_quantile_metrics")
+    return out
+
+
 def _raise_error_flags(flags: int, n_privacy_ids, n_partitions):
     if flags & 1:
         raise ValueError("privacy_id / partition_key outside the dense key range "
