@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PDP_ABI_VERSION 20
+#define PDP_ABI_VERSION 21
 
 /* error codes */
 #define PDP_OK 0
@@ -415,6 +415,43 @@ int pdp_reduce_quantile_leaves(const pdp_bound_config* cfg, const int64_t* priva
                                const uint8_t* pk_allowed, const void* value, int32_t value_kind, double min_value,
                                double max_value, void* workspace, uint64_t workspace_bytes, uint16_t* leaves,
                                uint32_t* offsets, void* stream);
+
+/* Most runs pdp_merge_quantile_leaves merges per partition: one per source
+ * rank of a process group (the project's multi-GPU scope is 8 ranks). */
+#define PDP_MAX_QUANTILE_RUNS 64
+
+/* Bytes of device workspace for pdp_merge_quantile_leaves: the run-major scan
+ * of the counts (4 B per run and partition) and a scan's chunk sums.
+ * n_runs outside [1, PDP_MAX_QUANTILE_RUNS]: PDP_E_UNSUPPORTED. */
+int pdp_quantile_merge_workspace_bytes(int32_t n_runs, int64_t n_partitions, uint64_t* bytes);
+
+/* QuantileCombiner.merge_accumulators (combiners.py:614-620) across the ranks
+ * of a process group, in columnar form: the owner of n_partitions partitions
+ * holds n_runs leaf arrays of the layout pdp_reduce_quantile_leaves writes,
+ * one per source rank, and gets one.  runs: device uint16[n_leaves], the
+ * arrays concatenated run-major, then partition-major; run s holds, for each
+ * partition p, run_counts[s * n_partitions + p] ascending codes (run_counts:
+ * device uint32[n_runs * n_partitions]).  n_leaves (host) is their total,
+ * n_leaves < 2^31; n_runs * n_partitions < 2^31.  On return
+ *   offsets[p] = the exclusive scan over p of sum_s run_counts[s][p], the
+ *     total in offsets[n_partitions] (device uint32[n_partitions + 1]);
+ *   leaves[offsets[p] .. offsets[p + 1]) = the ascending merge of the n_runs
+ *     runs of p (device uint16[n_leaves]; must not alias runs).
+ * Element j of run s of partition p, with code x, goes to offsets[p] + j + the
+ * number of codes <= x in the runs before s + the number of codes < x in the
+ * runs after s: a permutation, so every slot has one writer, there is no
+ * atomic, and two calls give the same bytes.  One thread per element and
+ * n_runs - 1 binary searches each.  1 <= n_runs <= PDP_MAX_QUANTILE_RUNS
+ * (else PDP_E_UNSUPPORTED); a workspace below
+ * pdp_quantile_merge_workspace_bytes returns PDP_E_WORKSPACE; both before
+ * any launch.  Nothing synchronises or allocates.  Every read of runs and
+ * every store to leaves is bounded by n_leaves on the device: counts whose sum
+ * is not n_leaves leave part of leaves unwritten or drop elements, and write
+ * nothing out of bounds.  n_leaves == 0 writes offsets only (runs and leaves
+ * may be NULL). */
+int pdp_merge_quantile_leaves(const uint16_t* runs, int64_t n_leaves, const uint32_t* run_counts, int32_t n_runs,
+                              int64_t n_partitions, void* workspace, uint64_t workspace_bytes, uint16_t* leaves,
+                              uint32_t* offsets, void* stream);
 
 /* QuantileCombiner.compute_metrics (combiners.py:622-633 ->
  * QuantileTree.compute_quantiles) for the kept partitions: for each i < n_kept

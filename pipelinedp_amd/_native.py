@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PIPELINEDP_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "lib", "libpipelinedp_amd.so")
 
 # constants (include/pipelinedp_amd.h)
-ABI_VERSION = 20
+ABI_VERSION = 21
 VALUE_NONE, VALUE_F64, VALUE_I64 = 0, 1, 2
 ACC_SUM, ACC_NSUM, ACC_NSUM2, SUM_PER_PARTITION, SUM_INT = 0x1, 0x2, 0x4, 0x8, 0x10
 DEBUG_CORRUPT_RECORDS = 0x40000000  # tests only (pipelinedp_amd.h)
@@ -40,6 +40,7 @@ MAX_VECTOR_SIZE = 4096      # PDP_MAX_VECTOR_SIZE
 NORM_LINF, NORM_L1, NORM_L2 = 0, 1, 2
 VECTOR_SUM_SLOT = 0x56454353  # Philox slot of the vector-sum noise ("VECS")
 MAX_QUANTILES = 64          # PDP_MAX_QUANTILES (ranks per pdp_quantile_metrics call)
+MAX_QUANTILE_RUNS = 64      # PDP_MAX_QUANTILE_RUNS (runs per partition in pdp_merge_quantile_leaves)
 QUANTILE_SLOT = 0x514E544C  # Philox slot of the quantile trees' noise ("QNTL")
 MAX_CONFIGURATIONS = 1024   # PDP_MAX_CONFIGURATIONS (utility analysis)
 UA_MAX_KEEP_TABLE = 1 << 20
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = (
     "pdp_vector_sum_metrics",
     "pdp_quantile_workspace_bytes",
     "pdp_reduce_quantile_leaves",
+    "pdp_quantile_merge_workspace_bytes",
+    "pdp_merge_quantile_leaves",
     "pdp_quantile_metrics",
     "pdp_dataset_histograms_workspace_bytes",
     "pdp_dataset_histograms",
@@ -275,6 +278,8 @@ def signatures():
         "pdp_quantile_workspace_bytes": (ctypes.c_int, [P(BoundConfig), P(u64)]),
         "pdp_reduce_quantile_leaves": (ctypes.c_int, [P(BoundConfig), vp, vp, vp, vp, i32, ctypes.c_double,
                                                       ctypes.c_double, vp, u64, vp, vp, vp]),
+        "pdp_quantile_merge_workspace_bytes": (ctypes.c_int, [i32, i64, P(u64)]),
+        "pdp_merge_quantile_leaves": (ctypes.c_int, [vp, i64, vp, i32, i64, vp, u64, vp, vp, vp]),
         "pdp_quantile_metrics": (ctypes.c_int, [vp, vp, i64, ctypes.c_double, ctypes.c_double, P(ctypes.c_double),
                                                 i32, P(NoiseParams), vp, i64, vp, i64, vp, u64, vp]),
         "pdp_dataset_histograms_workspace_bytes": (ctypes.c_int, [i64, i64, i64, P(u64)]),

@@ -17,6 +17,8 @@
 //   k_q_pack               the kept prefix as uint16 leaf codes
 //   k_quantile_metrics     one wave per kept partition, 16 lanes (the children
 //                          of the current node) per rank, four ranks a round
+//   k_q_merge              several ranks: the owner's merge of the ranks'
+//                          ascending runs, one array per partition again
 // No floating-point atomic; two runs on the same input give the same bytes.
 #include "pdp_quantile_plan.h"
 #include "pdp_segments.h"
@@ -174,6 +176,91 @@ __global__ void __launch_bounds__(kBlock) k_quantile_metrics(const uint16_t* __r
   }
 }
 
+// ------------------------------------------------ merge of the ranks' trees --
+// Under a process group a partition's owner receives one ascending run of
+// leaf codes per source rank (parallel.exchange_quantile_leaves) and needs one
+// ascending array per partition:
+//   scan_u32 (run_off)  run-major scan of the counts: where run s of partition p starts in `runs`
+//   k_q_merge_cols      per partition the sum of its runs' counts
+//   scan_u32 (offsets)  the merged arrays' offsets
+//   k_q_merge           one element per thread: its place is its own index in
+//                       its run plus, per other run of the partition, the
+//                       number of codes that go before it -- codes <= x in
+//                       the runs before its own, codes < x in the runs after
+// The places are a permutation (ties go by run, then by index): every slot has
+// one writer, no atomic, no LDS, and two calls give the same bytes.
+struct QMergeWs {
+  uint64_t run_off, chunks, total;
+};
+
+inline QMergeWs qmerge_layout(int32_t n_runs, int64_t P) {
+  QMergeWs w{};
+  const uint64_t cells = (uint64_t)n_runs * (uint64_t)P;
+  uint64_t off = 0;
+  w.run_off = off; off = align256(off + (cells + 1) * 4);
+  w.chunks = off; off = align256(off + (uint64_t)scan_chunk_sums_len((int64_t)cells) * 4);  // the longer of the two scans
+  w.total = off;
+  return w;
+}
+
+int qmerge_check(int32_t n_runs, int64_t P) {
+  if (n_runs < 1 || n_runs > PDP_MAX_QUANTILE_RUNS)
+    return set_error(PDP_E_UNSUPPORTED, "n_runs outside [1, PDP_MAX_QUANTILE_RUNS]");
+  if (P < 1) return set_error(PDP_E_INVALID, "n_partitions must be >= 1");
+  if ((int64_t)n_runs * P >= ((int64_t)1 << 31))
+    return set_error(PDP_E_UNSUPPORTED, "quantile merge: n_runs * n_partitions must be < 2^31");
+  return PDP_OK;
+}
+
+__global__ void __launch_bounds__(kBlock) k_q_merge_cols(int64_t P, int n_runs, const unsigned* __restrict__ counts,
+                                                         unsigned* __restrict__ col) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += stride) {
+    unsigned s = 0;
+    for (int r = 0; r < n_runs; ++r) s += counts[(int64_t)r * P + p];
+    col[p] = s;
+  }
+}
+
+// number of codes <= x in the ascending a[0..m)
+__device__ __forceinline__ unsigned q_upper_bound(const uint16_t* __restrict__ a, unsigned m, unsigned x) {
+  return q_lower_bound(a, m, x + 1);
+}
+
+// Every read of `runs` and every store to `leaves` stays below n: counts whose
+// scan disagrees with n (or wraps) shorten the runs that are read and drop the
+// stores that would fall outside, nothing else.
+__global__ void __launch_bounds__(kBlock) k_q_merge(const uint16_t* __restrict__ runs, int64_t n, int64_t P,
+                                                    int n_runs, const unsigned* __restrict__ run_off,
+                                                    const unsigned* __restrict__ off, uint16_t* __restrict__ leaves) {
+  const int64_t cells = (int64_t)n_runs * P;
+  const unsigned lim = (int64_t)run_off[cells] < n ? run_off[cells] : (unsigned)n;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < (int64_t)lim; e += stride) {
+    // the cell (run s, partition p) that holds e: the last one that starts at or before e
+    int64_t lo = 0, hi = cells;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)run_off[mid] <= e) lo = mid + 1; else hi = mid;
+    }
+    const int64_t cell = lo > 0 ? lo - 1 : 0;
+    const int s = (int)(cell / P);
+    const int64_t p = cell - (int64_t)s * P;
+    const unsigned x = runs[e];
+    const unsigned own = run_off[cell];
+    uint64_t at = (uint64_t)off[p] + ((unsigned)e >= own ? (unsigned)e - own : 0u);
+    for (int r = 0; r < n_runs; ++r) {
+      if (r == s) continue;
+      const int64_t c = (int64_t)r * P + p;
+      const unsigned b0 = run_off[c] < lim ? run_off[c] : lim;
+      const unsigned b1 = run_off[c + 1] < lim ? run_off[c + 1] : lim;
+      const unsigned m = b1 > b0 ? b1 - b0 : 0u;
+      at += r < s ? q_upper_bound(runs + b0, m, x) : q_lower_bound(runs + b0, m, x);
+    }
+    if (at < (uint64_t)n) leaves[at] = (uint16_t)x;
+  }
+}
+
 int quantile_check(const pdp_bound_config* cfg) {
   pdp_bound_plan_info info;
   const int rc = pdp_bound_plan(cfg, &info);
@@ -256,6 +343,49 @@ int pdp_reduce_quantile_leaves(const pdp_bound_config* cfg, const int64_t* priva
     cur ^= 1;
   }
   return launch("k_q_pack", k_q_pack, dim3(grid_for(n)), dim3(kBlock), 0, st, n, P, kr.off, leaf[cur], leaves);
+}
+
+int pdp_quantile_merge_workspace_bytes(int32_t n_runs, int64_t n_partitions, uint64_t* bytes) {
+  const int rc = qmerge_check(n_runs, n_partitions);
+  if (rc != PDP_OK) return rc;
+  if (bytes == nullptr) return set_error(PDP_E_INVALID, "bytes is NULL");
+  *bytes = qmerge_layout(n_runs, n_partitions).total;
+  return PDP_OK;
+}
+
+int pdp_merge_quantile_leaves(const uint16_t* runs, int64_t n_leaves, const uint32_t* run_counts, int32_t n_runs,
+                              int64_t n_partitions, void* workspace, uint64_t workspace_bytes, uint16_t* leaves,
+                              uint32_t* offsets, void* stream) {
+  int rc = qmerge_check(n_runs, n_partitions);
+  if (rc != PDP_OK) return rc;
+  if (n_leaves < 0) return set_error(PDP_E_INVALID, "n_leaves < 0");
+  if (n_leaves >= ((int64_t)1 << 31)) return set_error(PDP_E_UNSUPPORTED, "quantile merge: n_leaves must be < 2^31");
+  const QMergeWs w = qmerge_layout(n_runs, n_partitions);
+  if (workspace == nullptr || workspace_bytes < w.total)
+    return set_error(PDP_E_WORKSPACE, "workspace too small (see pdp_quantile_merge_workspace_bytes)");
+  if (run_counts == nullptr || offsets == nullptr) return set_error(PDP_E_INVALID, "run_counts or offsets is NULL");
+  if (n_leaves > 0 && (runs == nullptr || leaves == nullptr)) return set_error(PDP_E_INVALID, "runs or leaves is NULL");
+  if ((((uintptr_t)run_counts) & 3) || (((uintptr_t)offsets) & 3) || (((uintptr_t)workspace) & 3) ||
+      (((uintptr_t)runs) & 1) || (((uintptr_t)leaves) & 1))
+    return set_error(PDP_E_INVALID, "run_counts, offsets, workspace, runs and leaves must be aligned to their element size");
+  if (n_leaves > 0 && runs == leaves) return set_error(PDP_E_INVALID, "runs and leaves must not alias");
+
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t P = n_partitions, cells = (int64_t)n_runs * P;
+  unsigned* run_off = (unsigned*)(ws + w.run_off);
+  unsigned* chunks = (unsigned*)(ws + w.chunks);
+  PDP_HIP_CHECK(hipMemcpyAsync(run_off, run_counts, (uint64_t)cells * 4, hipMemcpyDeviceToDevice, st));
+  rc = launch("k_q_merge_cols", k_q_merge_cols, dim3(grid_for(P)), dim3(kBlock), 0, st, P, (int)n_runs, run_counts,
+              offsets);
+  if (rc != PDP_OK) return rc;
+  rc = scan_u32(run_off, cells, chunks, st);
+  if (rc != PDP_OK) return rc;
+  rc = scan_u32(offsets, P, chunks, st);
+  if (rc != PDP_OK) return rc;
+  if (n_leaves == 0) return PDP_OK;
+  return launch("k_q_merge", k_q_merge, dim3(grid_for(n_leaves)), dim3(kBlock), 0, st, runs, n_leaves, P, (int)n_runs,
+                run_off, offsets, leaves);
 }
 
 int pdp_quantile_metrics(const uint16_t* leaves, const uint32_t* offsets, int64_t n_partitions, double min_value,

@@ -774,6 +774,47 @@ def reduce_quantile_leaves(pid, pk, values, *, n_privacy_ids: int, n_partitions:
     return acc, leaves, offsets
 
 
+def merge_quantile_leaves(runs, run_counts, n_leaves: Optional[int] = None, *, workspace=None, stream=None):
+    """The quantile trees of several ranks merged per partition
+    (`pdp_merge_quantile_leaves`), as parallel.exchange_quantile_leaves
+    delivers them to the partitions' owner.
+
+    runs: int16 device tensor (uint16 bits), the ranks' leaf arrays
+    concatenated run-major, then partition-major; run_counts: int32
+    [n_runs, n_partitions] (uint32 bits), the ascending codes run s holds of
+    partition p; n_leaves: their total (host; defaults to len(runs)).
+    workspace: a uint8 device tensor of at least
+    pdp_quantile_merge_workspace_bytes (allocated when None).  Returns
+    (leaves, offsets) in the layout of reduce_quantile_leaves: leaves int16
+    [max(n_leaves, 1)], offsets int32 [n_partitions + 1]."""
+    torch = _torch()
+    lib = N.lib()
+    if not isinstance(run_counts, torch.Tensor) or run_counts.dim() != 2:
+        raise TypeError("run_counts must be a 2-D torch tensor [n_runs, n_partitions] on the GPU")
+    device = run_counts.device
+    n_runs, P = int(run_counts.shape[0]), int(run_counts.shape[1])
+    if run_counts.dtype != torch.int32:
+        raise TypeError(f"run_counts has dtype {run_counts.dtype}, expected torch.int32")
+    if not run_counts.is_contiguous():
+        raise ValueError("run_counts must be contiguous (row-major)")
+    _check_col(runs, "runs", (torch.int16,), int(runs.shape[0]) if isinstance(runs, torch.Tensor) else 0, device)
+    n_leaves = int(runs.shape[0]) if n_leaves is None else int(n_leaves)
+    if n_leaves < 0 or n_leaves > int(runs.shape[0]):
+        raise ValueError(f"n_leaves={n_leaves} is outside [0, {int(runs.shape[0])}]")
+    nbytes = ctypes.c_uint64(0)
+    N.check(lib.pdp_quantile_merge_workspace_bytes(n_runs, P, ctypes.byref(nbytes)),
+            "pdp_quantile_merge_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(max(int(nbytes.value), 256), dtype=torch.uint8, device=device)
+    _check_col(workspace, "workspace", (torch.uint8,), int(workspace.shape[0]), device)
+    leaves = torch.empty(max(n_leaves, 1), dtype=torch.int16, device=device)
+    offsets = torch.empty(P + 1, dtype=torch.int32, device=device)
+    N.check(lib.pdp_merge_quantile_leaves(_ptr(runs), n_leaves, _ptr(run_counts), n_runs, P, _ptr(workspace),
+                                          workspace.numel(), _ptr(leaves), _ptr(offsets), _stream(stream)),
+            "pdp_merge_quantile_leaves")
+    return leaves, offsets
+
+
 def quantile_metrics(leaves, offsets, index, *, min_value: float, max_value: float, ranks: Sequence[float],
                      noise: NoiseParams, seed: int, n_kept: Optional[int] = None, n_kept_dev=None,
                      partition_offset: int = 0, out=None, stream=None):

@@ -8,7 +8,12 @@ the dense per-partition accumulator arrays are summed across ranks with one
 reduce-scatter (RCCL over xGMI on MI355X; gloo in the CPU tests), after which
 rank r owns partitions [r * slice, (r + 1) * slice) and runs selection and
 noise on them locally (noise counters are global partition indices, so the
-result does not depend on the number of ranks).
+result does not depend on the number of ranks).  VECTOR_SUM's dense
+[partitions, vector_size] sums take the same route
+(exchange_vector_accumulator).  PERCENTILE's accumulator is a list per
+partition, not a sum: each rank sends every owner the contiguous span of leaf
+codes of the owner's partitions (exchange_quantile_leaves), and the owner
+merges the ranks' ascending runs on the device (executor.merge_quantile_leaves).
 """
 from typing import Dict, Optional, Tuple
 
@@ -85,6 +90,83 @@ def exchange_accumulators(acc: Dict[str, Optional["torch.Tensor"]], group=None, 
         for i, n in enumerate(names):
             out[n] = part[i]
     return out, rank * slice_len
+
+
+def exchange_vector_accumulator(vector_acc, group=None):
+    """VECTOR_SUM's accumulator ([padded partitions, vector_size] float64)
+    summed over the ranks: returns (this rank's [slice, vector_size] rows of the
+    sum, global index of the slice's first partition), by the two branches of
+    exchange_accumulators.  The identity on one rank."""
+    import torch
+    import torch.distributed as dist
+    world, rank = world_info(group)
+    if world == 1:
+        return vector_acc, 0
+    padded = int(vector_acc.shape[0])
+    if vector_acc.dim() != 2 or padded % world:
+        raise ValueError(f"vector accumulator of shape {tuple(vector_acc.shape)}: expected 2-D with a multiple of "
+                         f"world size {world} rows")
+    slice_len = padded // world
+    acc = vector_acc.contiguous()
+    if dist.get_backend(group) == "nccl":
+        part = torch.empty((slice_len, acc.shape[1]), dtype=acc.dtype, device=acc.device)
+        dist.reduce_scatter_tensor(part.view(-1), acc.view(-1), op=dist.ReduceOp.SUM, group=group)
+    else:  # gloo (CPU tests): all-reduce then keep the owned rows
+        wire = acc.cpu() if acc.is_cuda else acc.clone()
+        dist.all_reduce(wire, op=dist.ReduceOp.SUM, group=group)
+        part = wire[rank * slice_len:(rank + 1) * slice_len].to(acc.device).contiguous()
+    return part, rank * slice_len
+
+
+def exchange_quantile_leaves(leaves, offsets, group=None):
+    """PERCENTILE's accumulator exchange: every partition's ascending leaf
+    codes go to the rank that owns the partition.  leaves: int16 (uint16 bits),
+    partition-major, ascending within a partition; offsets: int32 (uint32
+    bits) of the padded length partition_slices(...)[0] + 1, as
+    executor.reduce_quantile_leaves returns them.  Rank r owns the partitions
+    [r * S, (r + 1) * S): the leaves of a rank's slice are one contiguous span,
+    so each rank sends to rank w the S counts of w's slice and
+    leaves[offsets[w * S] : offsets[(w + 1) * S]].  Returns (runs, run_counts,
+    n_leaves): runs int16, the spans received in source-rank order;
+    run_counts int32 [world, S], source rank s's counts of this rank's
+    partitions; n_leaves = len(runs) (host) -- the arguments of
+    executor.merge_quantile_leaves.  The split sizes (one int64 per rank) are
+    exchanged first and read on the host.  On one rank: (leaves, the counts as
+    [1, P], offsets[P]) with no collective."""
+    import torch
+    import torch.distributed as dist
+    world, rank = world_info(group)
+    n_off = int(offsets.shape[0])
+    counts = (offsets[1:] - offsets[:-1]).to(torch.int32)
+    if world == 1:
+        n = int(offsets[-1].item()) if n_off else 0
+        return leaves, counts.reshape(1, -1).contiguous(), n
+    if (n_off - 1) % world:
+        raise ValueError(f"offsets of length {n_off}: expected a multiple of world size {world}, plus one")
+    slice_len = (n_off - 1) // world
+    # the spans' ends, read on the host: world + 1 words
+    cuts = offsets[::slice_len].to(torch.int64).cpu()
+    in_sizes = (cuts[1:] - cuts[:-1]).tolist()
+    if min(in_sizes, default=0) < 0:
+        raise ValueError("offsets at or above 2^31: the quantile leaves of one rank must number fewer")
+    # the collectives take no 16-bit integers: the codes travel as their bytes
+    send = leaves[:int(cuts[-1])].contiguous().view(torch.uint8)
+    in_bytes = [2 * m for m in in_sizes]
+    if dist.get_backend(group) == "nccl":
+        sizes = torch.tensor(in_bytes, dtype=torch.int64, device=leaves.device)
+        got = torch.empty_like(sizes)
+        dist.all_to_all_single(got, sizes, group=group)
+        out_bytes = got.tolist()
+        run_counts = torch.empty((world, slice_len), dtype=torch.int32, device=counts.device)
+        dist.all_to_all_single(run_counts.view(-1), counts.contiguous(), group=group)
+        wire = torch.empty(sum(out_bytes), dtype=torch.uint8, device=leaves.device)
+        dist.all_to_all_single(wire, send, output_split_sizes=out_bytes, input_split_sizes=in_bytes, group=group)
+    else:  # gloo (CPU tests, 2-rank GPU test): host tensors through _exchange
+        (run_counts,) = _exchange([counts], torch.full((world,), slice_len, dtype=torch.int64), group)
+        run_counts = run_counts.reshape(world, slice_len)
+        (wire,) = _exchange([send], torch.tensor(in_bytes, dtype=torch.int64), group)
+    runs = wire.contiguous().view(leaves.dtype)
+    return runs, run_counts.contiguous(), int(runs.shape[0])
 
 
 def shard_by_privacy_id(privacy_ids, world: int, rank: int):
@@ -522,7 +604,8 @@ def shuffle_by_privacy_id(ident, columns, group=None):
     """Moves every row to the rank that owns its privacy id (identity):
     returns (identities, columns) of the rows this rank now holds, in
     (source rank, source order) order — deterministic for a fixed input.
-    `columns` may hold None entries (passed through as None)."""
+    `columns` may hold None entries (passed through as None) and 2-D columns
+    ([n, d], e.g. VECTOR_SUM's vectors: whole rows move)."""
     import torch
     world, _ = world_info(group)
     if world == 1:
